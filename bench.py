@@ -2,7 +2,9 @@
 """bench.py -- headline benchmark: knn_points B=32 N=M=65536 K=16 D=3 fp32 per GPU
 (BASELINE.json configs[1]; metric "Mpoint-pairs/s (+ %HBM roofline) knn_points ...").
 
-    python bench.py                                   # 1 GPU
+    python bench.py                                   # 1 GPU: the headline line only
+    python bench.py --full                            # + grid reuse, CPU baseline (multi-rank: + sharded chamfer)
+    python bench.py --dump-outputs DIR                # + a fixed sample of the last step's outputs as DIR/*.npy
     python bench.py --gpus 4 --steps 20 --warmup 5    # spawns 4 ranks itself (one process per GPU, RCCL); fails fast
     python bench.py --gpus 8 --scaling strong         # BASELINE.json configs[4]: B=256 split over the ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -23,8 +25,11 @@ bytes (4*D*(P1+P2) + P1*K*12 bytes per cloud = 452,984,832
 launch) over the HIP-event duration of the launch, measured live on the launch stream;
 `roofline.traffic` and `roofline.valu_issue` come from committed rocprofv3 counter passes of this
 same command and are nulled when the kernel sources changed since they were taken.
-`cpu_baseline` is the reference's own CPU kernel (oracle/_ref, kind "reference") or the C oracle
+`cpu_baseline` (--full) is the reference's own CPU kernel (oracle/_ref, kind "reference") or the C oracle
 (kind "port") timed on a bounded sample of the same workload.
+
+A plain run sets up, warms up, times the steps, writes the outputs (--dump-outputs) and prints the line;
+every other measurement (grid reuse, CPU baseline, sharded chamfer) runs only with --full, after all of that.
 """
 import argparse
 import hashlib
@@ -53,16 +58,25 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, also run the secondary measurements: grid reuse and CPU baseline "
+                         "(1-GPU runs), sharded chamfer (multi-rank runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the last step's outputs "
+                         "(rank 0's clouds) as DIR/idx.npy (float64) and DIR/dists.npy (float32)")
     ap.add_argument("--cpu-sample-queries", type=int, default=24576,
-                    help="queries of the CPU-baseline sample (0 disables); ~10-20 s of CPU work")
+                    help="--full: queries of the CPU-baseline sample (0 disables); ~10-20 s of CPU work")
     ap.add_argument("--cpu-all-cores", action="store_true",
-                    help="also time the CPU kernel on every host core (query blocks over a thread pool)")
+                    help="--full: also time the CPU kernel on every host core (query blocks over a thread pool)")
     ap.add_argument("--version", type=int, default=-1, help="knn kernel family (-1 auto)")
     ap.add_argument("--reuse-steps", type=int, default=10,
-                    help="1-GPU runs: timed steps of the opt-in grid reuse after the headline region (0 disables)")
+                    help="--full, 1-GPU runs: timed steps of the opt-in grid reuse after the headline region (0 disables)")
     ap.add_argument("--chamfer-steps", type=int, default=3,
-                    help="multi-rank runs: timed sharded chamfer fwd+bwd steps after the KNN region (0 disables)")
-    return ap.parse_args(argv)
+                    help="--full, multi-rank runs: timed sharded chamfer fwd+bwd steps after the KNN region (0 disables)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -251,6 +265,28 @@ def cpu_baseline(p1, p2, sample_queries: int, threads: int = 1):
     }, idx
 
 
+# the --dump-outputs sample: at most DUMP_ROWS query rows of the last step, K neighbours each (idx as float64,
+# dists as float32: 48 MiB at most), the same rows for the same arguments in every run
+DUMP_ROWS, DUMP_SEED = 262144, 7000
+
+
+def dump_outputs(out_dir, idx, dists):
+    """Write a fixed seeded sample of query rows of (idx, dists) -- (N, P1, K) each -- as DIR/idx.npy, DIR/dists.npy."""
+    import numpy as np
+    import torch
+
+    rows = idx.shape[0] * idx.shape[1]
+    pick = np.arange(rows) if rows <= DUMP_ROWS else np.sort(
+        np.random.default_rng(DUMP_SEED).choice(rows, DUMP_ROWS, replace=False))
+    pick_t = torch.from_numpy(pick).to(idx.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "idx.npy"),
+            idx.reshape(rows, -1).index_select(0, pick_t).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "dists.npy"),
+            dists.reshape(rows, -1).index_select(0, pick_t).cpu().numpy().astype(np.float32))
+    log(f"wrote {len(pick)} of {rows} query rows of idx / dists to {out_dir}")
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -331,6 +367,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out[0], out[1])
     kern_ms = [a.elapsed_time(b) for a, b in ev]
     avg_kern_s = float(np.mean(kern_ms)) / 1e3
 
@@ -400,7 +438,7 @@ def main():
         },
     }
 
-    if world == 1 and args.reuse_steps > 0:
+    if args.full and world == 1 and args.reuse_steps > 0:
         # Outside the headline region (which rebuilds the grid every step, like the reference's stateless operator):
         # the opt-in grid reuse of repeated queries against an unmodified target (pointops_knn_points_idx_reuse).
         import pytorch3d_pointops_amd as po
@@ -435,7 +473,7 @@ def main():
             "note": "opt-in (set_grid_cache): the workspace of the previous call is handed back when the target tensors are "
                     "unmodified (object, data pointer, version counter); NOT part of `value`, which rebuilds every step",
         }
-    if rank == 0 and world == 1 and args.cpu_sample_queries > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample_queries > 0:
         log("timing the CPU baseline sample ...")
         cb, cpu_idx = cpu_baseline(p1_h, p2_h, args.cpu_sample_queries)
         result["cpu_baseline"] = cb
@@ -446,7 +484,7 @@ def main():
             n = os.cpu_count() or 1
             cb_all, _ = cpu_baseline(p1_h, p2_h, args.cpu_sample_queries * min(n, 8), threads=n)
             result["cpu_baseline_all_cores"] = cb_all
-    if use_dist and args.chamfer_steps > 0:
+    if args.full and use_dist and args.chamfer_steps > 0:
         # Outside the KNN region: the path's one real exchange -- chamfer's batch reduction over clouds
         # sharded across ranks = one RCCL all_gather of the per-cloud loss vectors (fwd + bwd timed).
         from pytorch3d_pointops_amd.sharded import sharded_chamfer_distance

@@ -14,6 +14,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
+#include "zero_fill.h"
 
 namespace pointops {
 
@@ -171,9 +172,9 @@ __global__ __launch_bounds__(kDetBlock) void det_gather_kernel(const float* __re
 static int det_invert(const DetWs& ws, const int64_t* idx, const int64_t* lengths1, const int64_t* lengths2, int64_t N,
                       int64_t L, int64_t K, int64_t M, hipStream_t stream) {
   const int64_t T = N * L * K, targets = N * M;
-  if (hipMemsetAsync(ws.seg_start, 0, sizeof(int) * (size_t)(targets + 1), stream) != hipSuccess ||
-      hipMemsetAsync(ws.seg_end, 0, sizeof(int) * (size_t)(targets + 1), stream) != hipSuccess)
-    return check_launch("deterministic backward (memset)");
+  int zrc = zero_words_async(ws.seg_start, targets + 1, stream, "deterministic backward (zero)");
+  if (zrc == POINTOPS_OK) zrc = zero_words_async(ws.seg_end, targets + 1, stream, "deterministic backward (zero)");
+  if (zrc != POINTOPS_OK) return zrc;
   if (T == 0) return POINTOPS_OK;
   const unsigned blocks = (unsigned)ceil_div(T, kDetBlock);
   hipLaunchKernelGGL(det_keys_kernel, dim3(blocks), dim3(kDetBlock), 0, stream, idx, lengths1, lengths2, T, (int)L,

@@ -9,6 +9,7 @@
 // the result is deterministic run to run.
 #include "common.h"
 #include "debug.h"
+#include "zero_fill.h"
 
 namespace pointops {
 
@@ -404,12 +405,12 @@ static int chamfer_backward_impl(const float* x, const float* y, const int64_t* 
   const int rc = cf_fill(&ft, F, x_feats, y_feats, grad_x_feats, grad_y_feats, C);
   if (rc != POINTOPS_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  if (!acc && N * P2 * D > 0 && hipMemsetAsync(grad_y, 0, sizeof(float) * (size_t)(N * P2 * D), stream) != hipSuccess)
-    return check_launch("chamfer_backward(memset)");
-  for (int f = 0; f < F; ++f)
-    if (!acc && N * P2 * C[f] > 0 &&
-        hipMemsetAsync(grad_y_feats[f], 0, sizeof(float) * (size_t)(N * P2 * C[f]), stream) != hipSuccess)
-      return check_launch("chamfer_backward(memset)");
+  if (!acc) {
+    int zrc = zero_words_async(grad_y, N * P2 * D, stream, "chamfer_backward(zero)");
+    for (int f = 0; f < F && zrc == POINTOPS_OK; ++f)
+      zrc = zero_words_async(grad_y_feats[f], N * P2 * C[f], stream, "chamfer_backward(zero)");
+    if (zrc != POINTOPS_OK) return zrc;
+  }
   if (N == 0 || P1 == 0) return POINTOPS_OK;
   bool four = D <= 4;
   for (int f = 0; f < F; ++f) four = four && C[f] <= 4;

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "debug.h"
+#include "zero_fill.h"
 
 namespace pointops {
 
@@ -677,8 +678,8 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
         mode = 0;
       }
       if (G > 1) {
-        if (hipMemsetAsync(ex, 0, slot_bytes + sizeof(unsigned) * (size_t)N, stream) != hipSuccess)
-          return check_launch("fps(memset)");
+        const int zrc = zero_words_async(ex, (int64_t)(slot_bytes / sizeof(unsigned)) + N, stream, "fps(zero)");
+        if (zrc != POINTOPS_OK) return zrc;
       }
       // XCD-local numbering: cluster c = (j / G) * 8 + x for the j-th block of XCD group x
       const int blocks = mode == 0 ? n_clusters * G : (int)ceil_div(n_clusters, kXcds) * G * kXcds;

@@ -10,6 +10,7 @@
 // (tiled_scatter.h) when U <= 4 and the table is large, fp32 device atomics otherwise.
 #include "common.h"
 #include "tiled_scatter.h"
+#include "zero_fill.h"
 
 namespace pointops {
 
@@ -164,8 +165,8 @@ extern "C" int pointops_gather_neighbors_backward(const float* grad_out, const i
   hipStream_t stream = (hipStream_t)stream_;
   const TiledPlan plan = tiled_plan(N, L, K, M, (int)U, "gather_bwd_mode", "gather_bwd_split");
   if (N * M * U > 0 && !(plan.tiled && plan.S == 1)) {
-    if (hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)(N * M * U), stream) != hipSuccess)
-      return check_launch("gather_neighbors_backward(memset)");
+    const int zrc = zero_words_async(grad_x, N * M * U, stream, "gather_neighbors_backward(zero)");
+    if (zrc != POINTOPS_OK) return zrc;
   }
   const int64_t total = N * L * K * U;
   if (total == 0) return POINTOPS_OK;

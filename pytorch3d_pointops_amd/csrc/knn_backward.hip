@@ -11,6 +11,7 @@
 //   c = 2*g*(p1-p2) for L2, g*sign(p1>p2) for L1.
 #include "common.h"
 #include "tiled_scatter.h"
+#include "zero_fill.h"
 
 namespace pointops {
 
@@ -262,8 +263,8 @@ extern "C" int pointops_knn_points_backward(const float* p1, const float* p2,
   const bool tiled = plan.tiled;
   const int S = plan.S;
   if (N * P2 * D > 0 && !(tiled && S == 1)) {
-    if (hipMemsetAsync(grad_p2, 0, sizeof(float) * (size_t)(N * P2 * D), stream) != hipSuccess)
-      return check_launch("knn_points_backward(memset)");
+    const int zrc = zero_words_async(grad_p2, N * P2 * D, stream, "knn_points_backward(zero)");
+    if (zrc != POINTOPS_OK) return zrc;
   }
   if (N == 0 || P1 == 0) return POINTOPS_OK;
   if (D <= 4) {

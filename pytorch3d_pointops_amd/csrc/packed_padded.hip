@@ -12,6 +12,7 @@
 // D=3).  Grid = (element chunks, clouds) so ragged batches still fill the chip.
 // packed_to_padded writes its zero padding itself (no separate memset pass).
 #include "common.h"
+#include "zero_fill.h"
 
 namespace pointops {
 
@@ -88,8 +89,8 @@ extern "C" int pointops_padded_to_packed(const float* padded, const int64_t* fir
   hipStream_t stream = (hipStream_t)stream_;
   if (F * D > 0) {
     // rows owned by no cloud stay zero (reference: at::zeros, ..._cpu.cpp:52-53)
-    if (hipMemsetAsync(packed, 0, sizeof(float) * (size_t)(F * D), stream) != hipSuccess)
-      return check_launch("padded_to_packed(memset)");
+    const int zrc = zero_words_async(packed, F * D, stream, "padded_to_packed(zero)");
+    if (zrc != POINTOPS_OK) return zrc;
   }
   if (B == 0 || max_size == 0 || F == 0) return POINTOPS_OK;
   const int64_t chunks = ceil_div(max_size * D, (int64_t)kPpBlock * kPpPerThread);

@@ -257,3 +257,12 @@ def example2_inputs():
                             (u(3164, (800, 1)) * 0.8 + 0.2).astype(np.float32)],
                    values=[normalish(3165, (1000, 4)), normalish(3166, (800, 4))]),
     )
+
+
+def ref_random_case():
+    """Seeded inputs beyond the small fixtures: knn (norm 1 / 2, K 1 / 16), ball query and FPS
+    on two ragged clouds (tests/golden/ref_random.npz holds the reference's outputs on them)."""
+    return dict(p1=cloud(801, (2, 700, 3)), p2=cloud(802, (2, 2000, 3)),
+                l1=np.array([700, 512]), l2=np.array([2000, 1777]),
+                knn=[(norm, K) for norm in (1, 2) for K in (1, 16)], bq_K=32, bq_radius=0.2,
+                fps_K=np.array([300, 100]), fps_start=np.array([5, 0]))

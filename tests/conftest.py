@@ -28,17 +28,6 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def ref_oracle():
-    """The reference's own compiled CPU kernels (oracle/_ref), when present."""
-    from oracle.oracle import load_ref
-
-    r = load_ref()
-    if r is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference; see oracle/build_ref.py)")
-    return r
-
-
-@pytest.fixture(scope="session")
 def dev():
     import torch
 

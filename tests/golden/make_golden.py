@@ -434,6 +434,21 @@ def gen_pointclouds():
     save("pointclouds_api", **out)
 
 
+def gen_ref_random():
+    c = cases.ref_random_case()
+    p1, p2, l1, l2 = T(c["p1"]), T(c["p2"]), T(c["l1"]), T(c["l2"])
+    out = {}
+    for norm, K in c["knn"]:
+        i, d = ref_C.knn_points_idx(p1, p2, l1, l2, norm, K, -1)
+        out[f"knn_n{norm}_k{K}/idx"] = i.numpy().astype(np.int32)
+        out[f"knn_n{norm}_k{K}/dists"] = d.numpy()
+    i, d = ref_C.ball_query(p1, p2, l1, l2, c["bq_K"], c["bq_radius"])
+    out["ball_query/idx"] = i.numpy().astype(np.int32)
+    out["ball_query/dists"] = d.numpy()
+    out["fps/idx"] = ref_C.sample_farthest_points(p2, l2, T(c["fps_K"]), T(c["fps_start"])).numpy().astype(np.int32)
+    save("ref_random", **out)
+
+
 def gen_big():
     """cfg2-size single clouds: digests + sampled rows (the full idx would be 8 MB per cloud)."""
     meta = {}
@@ -488,5 +503,6 @@ if __name__ == "__main__":
     gen_examples()
     gen_examples2()
     gen_pointclouds()
+    gen_ref_random()
     if "--big" in sys.argv:
         gen_big()

@@ -101,6 +101,44 @@ def test_graph_chamfer_forward_backward(dev, N, P1, P2, normals):
             assert (np.abs(u - v) <= tol).all()
 
 
+def _accumulating_case(op, dev):
+    from pytorch3d_pointops_amd.functions import knn_gather, knn_points
+    from pytorch3d_pointops_amd.functions.chamfer import chamfer_distance
+
+    if op == "chamfer":
+        lx = torch.tensor([2048, 1500, 1100, 2000], device=dev)
+        ly = torch.tensor([1500, 800, 1400, 1000], device=dev)
+        ins = [_cloud(30, (4, 2048, 3), dev).requires_grad_(True), _cloud(31, (4, 1500, 3), dev).requires_grad_(True)]
+        return (lambda x, y: chamfer_distance(x, y, x_lengths=lx, y_lengths=ly)[0]), ins
+    if op == "knn_backward":
+        ins = [_cloud(32, (2, 1024, 3), dev).requires_grad_(True), _cloud(33, (2, 1500, 3), dev).requires_grad_(True)]
+        return (lambda x, y: knn_points(x, y, K=4).dists.sum()), ins
+    idx = torch.randint(0, 1500, (2, 1024, 8), generator=torch.Generator().manual_seed(34)).to(dev)
+    return (lambda x: knn_gather(x, idx).sum()), [_cloud(35, (2, 1500, 3), dev).requires_grad_(True)]
+
+
+@pytest.mark.parametrize("op", ["chamfer", "knn_backward", "gather_backward"])
+def test_graph_relaunches_rezero_accumulated_gradients(dev, op):
+    """Backward passes that zero a gradient before accumulating into it, replayed three times with the graph's
+    gradient buffers filled with NaN before every replay: each replay must rewrite all of them (a captured
+    hipMemsetAsync stops writing zeros from the graph's second launch on under ROCm 7.0; the library zeroes with
+    kernels)."""
+    from pytorch3d_pointops_amd import graphs
+
+    fn, ins = _accumulating_case(op, dev)
+    step = graphs.capture(fn, ins, backward=True)
+    eager = [t.detach().clone().requires_grad_(True) for t in ins]
+    want = torch.autograd.grad(fn(*eager), eager)
+    for _ in range(3):
+        for g in step.grads:
+            g.fill_(float("nan"))
+        _, got = step()
+        for u, v in zip(got, want):
+            u, v = u.cpu().numpy(), v.cpu().numpy()
+            tol = 2e-5 * np.abs(v) + 2e-6 * max(1e-3, float(np.abs(v).max()))
+            assert (np.abs(u - v) <= tol).all()
+
+
 def test_graph_bypasses_grid_reuse(dev):
     import pytorch3d_pointops_amd as pa
     from pytorch3d_pointops_amd import _C, graphs
