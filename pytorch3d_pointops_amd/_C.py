@@ -162,6 +162,17 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _workspace(nbytes: int, dev):
+    """Device scratch of one native call, or None when it needs none.  A fresh tensor per call: the caching allocator
+    is stream-ordered (the block is handed out again only behind this call's launches), and inside a HIP-graph capture
+    it comes from the graph's private pool (graphs.py)."""
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 # ---------------------------------------------------------------------------
 # Grid reuse (opt-in): the cell grid of the exact search is an index over p2 -- bounding boxes, cell tables, the
 # cell-sorted copy of the cloud, refined cells: 123 us of a 705 us call at B=32, N=M=65536, K=16 -- that a second
@@ -169,9 +180,9 @@ def _stream():
 # by further queries).  With the switch on, knn_points_idx keeps the workspaces of its last few grid calls and hands
 # them back to the C ABI (pointops_knn_points_idx_reuse) when the target tensors are provably the ones it was built
 # from: the same tensor OBJECTS (weak references), the same data pointers and the same autograd version counters --
-# every in-place op of PyTorch bumps that counter.  It is OFF by default because one kind of write is invisible to
-# it: `p2.data.copy_(...)` / a raw-pointer write from another library changes the bytes without the counter, and a
-# stale grid then answers for the OLD points (the reference's stateless operator has no such failure mode).
+# every in-place op of PyTorch bumps that counter.  It is OFF by default because some writes are invisible to it
+# (set_grid_cache lists them), and a stale grid then answers for the OLD points (the reference's stateless operator
+# has no such failure mode).
 #   pytorch3d_pointops_amd.set_grid_cache(True [, max_entries])      or      POINTOPS_GRID_CACHE=1
 # ---------------------------------------------------------------------------
 import collections
@@ -184,7 +195,12 @@ grid_cache_stats = {"miss": 0, "points": 0, "both": 0}
 
 
 def set_grid_cache(enabled: bool, max_entries: int = 2) -> None:
-    """Switch the grid reuse of knn_points_idx on or off (off: the default; cached workspaces are dropped)."""
+    """Switch the grid reuse of knn_points_idx on or off (off: the default; cached workspaces are dropped).
+
+    The cache trusts a target tensor whose object, data pointer and version counter are unchanged.  Writes that change
+    its bytes without bumping the counter are NOT seen, and the reused grid then answers for the old points:
+    `p2.data.copy_(...)`, a raw-pointer write from another library, a HIP-graph replay that rewrites `p2` (graphs.py),
+    and writes through a DLPack or numpy alias of its storage."""
     global _GRID_CACHE_ON, _GRID_CACHE_MAX
     _GRID_CACHE_ON = bool(enabled)
     _GRID_CACHE_MAX = max(1, int(max_entries))
@@ -192,33 +208,13 @@ def set_grid_cache(enabled: bool, max_entries: int = 2) -> None:
         _GRID_CACHE.clear()
 
 
-_SCRATCH = {}
-
-
-def _scratch(nbytes: int, dev):
-    """Workspace for one call.  Small ones (<= 4 MiB: the sliced brute-force scans of small batches) come from a grow-only
-    buffer per (device, stream): every user enqueues on that stream, in order, so the buffer can be handed out again at
-    once and a small call saves an allocator round trip (~2 us).  Big ones are allocated per call."""
-    if nbytes > (4 << 20) or torch.cuda.is_current_stream_capturing():
-        # (inside a HIP-graph capture the buffer must belong to the graph's private pool: graphs.py)
-        return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    key = (dev.index, _stream())
-    buf = _SCRATCH.get(key)
-    if buf is None or buf.numel() < nbytes:
-        if len(_SCRATCH) > 32:
-            _SCRATCH.clear()
-        buf = torch.empty((max(nbytes, 1 << 16),), dtype=torch.uint8, device=dev)
-        _SCRATCH[key] = buf
-    return buf
-
-
 def _sig(t):
     return (id(t), t._version, t.data_ptr(), tuple(t.shape))
 
 
 def _grid_workspace(p1, p2, lengths1, lengths2, shape, ws_bytes, dev):
-    """(workspace, reuse level) for a grid call: level 2 when both point sets are the cached call's, 1 when the
-    target side is, 0 (a fresh workspace, remembered) otherwise."""
+    """(workspace, reuse level, cache key) for a grid call: level 2 when both point sets are the cached call's, 1 when
+    the target side is, 0 (a fresh workspace, remembered) otherwise.  The caller drops the key if its call fails."""
     key = (_sig(p2), _sig(lengths2), shape, _stream(), str(dev))
     hit = _GRID_CACHE.get(key)
     if hit is not None and hit["p2"]() is p2 and hit["l2"]() is lengths2 and hit["ws"].numel() == ws_bytes:
@@ -227,16 +223,16 @@ def _grid_workspace(p1, p2, lengths1, lengths2, shape, ws_bytes, dev):
         level = 2 if (hit["q"] == q and hit["p1"]() is p1 and hit["l1"]() is lengths1) else 1
         hit.update(q=q, p1=weakref.ref(p1), l1=weakref.ref(lengths1))
         grid_cache_stats["both" if level == 2 else "points"] += 1
-        return hit["ws"], level
+        return hit["ws"], level, key
     grid_cache_stats["miss"] += 1
     for k in [k for k, v in _GRID_CACHE.items() if v["p2"]() is None]:
         del _GRID_CACHE[k]  # entries whose target tensor has died
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     _GRID_CACHE[key] = dict(ws=ws, p2=weakref.ref(p2), l2=weakref.ref(lengths2), q=(_sig(p1), _sig(lengths1)),
                             p1=weakref.ref(p1), l1=weakref.ref(lengths1))
     while len(_GRID_CACHE) > _GRID_CACHE_MAX:
         _GRID_CACHE.popitem(last=False)
-    return ws, 0
+    return ws, 0, key
 
 
 # ---------------------------------------------------------------------------
@@ -260,53 +256,25 @@ def knn_points_idx(p1, p2, lengths1, lengths2, norm: int, K: int, version: int =
         idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
         dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
         ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, K, version)
-        reuse = 0
         if _GRID_CACHE_ON and ws_bytes and _lib.pointops_knn_uses_grid(N, P1, P2, D, int(K), int(version)) \
                 and not torch.cuda.is_current_stream_capturing():  # (a captured call must not bake a reuse level in)
-            ws, reuse = _grid_workspace(p1, p2, lengths1, lengths2, (N, P1, P2, D, int(K), int(version)), ws_bytes, dev)
+            ws, reuse, key = _grid_workspace(p1, p2, lengths1, lengths2, (N, P1, P2, D, int(K), int(version)),
+                                             ws_bytes, dev)
         else:
-            ws = _scratch(ws_bytes, dev) if ws_bytes else None
-        _check(
-            _lib.pointops_knn_points_idx_reuse(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
-                                               lengths2.data_ptr(), N, P1, P2, D, int(norm), int(K),
-                                               int(version), idxs.data_ptr(), dists.data_ptr(),
-                                               ws.data_ptr() if ws is not None else None, ws_bytes, reuse,
-                                               _stream()),
-            "knn_points_idx",
-        )
+            ws, reuse, key = _workspace(ws_bytes, dev), 0, None
+        try:
+            _check(_lib.pointops_knn_points_idx_reuse(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
+                                                      lengths2.data_ptr(), N, P1, P2, D, int(norm), int(K),
+                                                      int(version), idxs.data_ptr(), dists.data_ptr(), _ptr(ws),
+                                                      ws_bytes, reuse, _stream()), "knn_points_idx")
+        except Exception:
+            _GRID_CACHE.pop(key, None)  # a failed call may have left the grid half built
+            raise
     return idxs, dists
 
 
-def knn_grid_fallback_counts(p1, p2, lengths1, lengths2, norm: int, K: int):
-    """Diagnostics: run the grid family (version 3) and return (idx, dists, counts) where
-    counts[0, n] = queries of cloud n re-searched wave-per-query on a growing cell cube,
-    counts[1, n] = queries that ended in the whole-cloud scan."""
-    dev = _require_gpu(p1, p2, lengths1, lengths2)
-    p1, p2 = p1.contiguous(), p2.contiguous()
-    N, P1, D = p1.shape
-    P2 = p2.shape[1]
-    if not knn_check_version(3, D, K):
-        raise RuntimeError("grid family needs D <= 3 and K <= 128")
-    with _on(dev):
-        idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
-        ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, K, 3)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        counts = torch.zeros((2, N), dtype=torch.int32, device=dev)
-        _check(_lib.pointops_knn_points_idx(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
-                                            lengths2.data_ptr(), N, P1, P2, D, int(norm), int(K), 3,
-                                            idxs.data_ptr(), dists.data_ptr(), ws.data_ptr(), ws_bytes,
-                                            _stream()), "knn_points_idx")
-        _check(_lib.pointops_knn_grid_fallback_counts(ws.data_ptr(), N, P1, P2, int(K), counts.data_ptr(),
-                                                      _stream()), "knn_grid_fallback_counts")
-    return idxs, dists, counts
-
-
-def knn_grid_stats(p1, p2, lengths1, lengths2, norm: int, K: int):
-    """Diagnostics: run the grid family and return (idx, dists, stats (N, 14) int32): cells per dimension (3),
-    cell count, grid used, queries uncertified after the lane pass / the quad + box passes / sent to the whole-cloud
-    scan, queries deferred to the box search, refined cells, bins of the point / query sort, crowded bins of the
-    point / query sort."""
+def _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, out_shape, read, what):
+    """Run the grid family (version 3), then `read` copies what it left in its workspace into an int32 tensor."""
     dev = _require_gpu(p1, p2, lengths1, lengths2)
     p1 = p1.contiguous()
     p2 = p1 if p2 is p1 else p2.contiguous()
@@ -318,15 +286,31 @@ def knn_grid_stats(p1, p2, lengths1, lengths2, norm: int, K: int):
         idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
         dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
         ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, K, 3)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        stats = torch.zeros((N, 14), dtype=torch.int32, device=dev)
+        ws = _workspace(ws_bytes, dev)
+        out = torch.zeros(out_shape(N), dtype=torch.int32, device=dev)
         _check(_lib.pointops_knn_points_idx(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
                                             lengths2.data_ptr(), N, P1, P2, D, int(norm), int(K), 3,
-                                            idxs.data_ptr(), dists.data_ptr(), ws.data_ptr(), ws_bytes,
+                                            idxs.data_ptr(), dists.data_ptr(), _ptr(ws), ws_bytes,
                                             _stream()), "knn_points_idx")
-        _check(_lib.pointops_knn_grid_stats(ws.data_ptr(), N, P1, P2, int(K), stats.data_ptr(), _stream()),
-               "knn_grid_stats")
-    return idxs, dists, stats
+        _check(read(_ptr(ws), N, P1, P2, int(K), out.data_ptr(), _stream()), what)
+    return idxs, dists, out
+
+
+def knn_grid_fallback_counts(p1, p2, lengths1, lengths2, norm: int, K: int):
+    """Diagnostics: run the grid family (version 3) and return (idx, dists, counts) where
+    counts[0, n] = queries of cloud n re-searched wave-per-query on a growing cell cube,
+    counts[1, n] = queries that ended in the whole-cloud scan."""
+    return _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, lambda N: (2, N),
+                             _lib.pointops_knn_grid_fallback_counts, "knn_grid_fallback_counts")
+
+
+def knn_grid_stats(p1, p2, lengths1, lengths2, norm: int, K: int):
+    """Diagnostics: run the grid family and return (idx, dists, stats (N, 14) int32): cells per dimension (3),
+    cell count, grid used, queries uncertified after the lane pass / the quad + box passes / sent to the whole-cloud
+    scan, queries deferred to the box search, refined cells, bins of the point / query sort, crowded bins of the
+    point / query sort."""
+    return _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, lambda N: (N, 14), _lib.pointops_knn_grid_stats,
+                             "knn_grid_stats")
 
 
 def knn_check_version(version: int, D: int, K: int) -> bool:
@@ -359,12 +343,12 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm: int, grad_dists,
         grad_p2 = torch.empty((N, P2, D), dtype=torch.float32, device=dev)
         if deterministic:
             ws_bytes = _lib.pointops_backward_det_workspace_bytes(N, P1, K, P2)
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            ws = _workspace(ws_bytes, dev)
             _check(
                 _lib.pointops_knn_points_backward_det(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
                                                       lengths2.data_ptr(), idxs.data_ptr(), grad_dists.data_ptr(),
                                                       N, P1, P2, D, K, int(norm), grad_p1.data_ptr(),
-                                                      grad_p2.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+                                                      grad_p2.data_ptr(), _ptr(ws), ws_bytes, _stream()),
                 "knn_points_backward(deterministic)",
             )
             return grad_p1, grad_p2
@@ -398,12 +382,11 @@ def ball_query(p1, p2, lengths1, lengths2, K: int, radius: float):
         idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
         dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
         ws_bytes = _lib.pointops_ball_query_workspace_bytes(N, P1, P2, D, int(K))
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
+        ws = _workspace(ws_bytes, dev)
         _check(
             _lib.pointops_ball_query(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
                                      lengths2.data_ptr(), N, P1, P2, D, int(K), float(radius),
-                                     idxs.data_ptr(), dists.data_ptr(),
-                                     ws.data_ptr() if ws is not None else None, ws_bytes, _stream()),
+                                     idxs.data_ptr(), dists.data_ptr(), _ptr(ws), ws_bytes, _stream()),
             "ball_query",
         )
     return idxs, dists
@@ -430,11 +413,11 @@ def sample_farthest_points(points, lengths, K, start_idxs, max_K=None):
     with _on(dev):
         idxs = torch.empty((N, max_K), dtype=torch.int64, device=dev)
         ws_bytes = _lib.pointops_fps_workspace_bytes(N, P, max_K)
-        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev)
         _check(
             _lib.pointops_sample_farthest_points(points.data_ptr(), lengths.data_ptr(), K.data_ptr(),
                                                  start_idxs.data_ptr(), N, P, D, max_K,
-                                                 idxs.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+                                                 idxs.data_ptr(), _ptr(ws), ws_bytes, _stream()),
             "sample_farthest_points",
         )
     return idxs
@@ -534,9 +517,8 @@ def gather_neighbors(x, idx, lengths=None):
     with _on(dev):
         out = torch.empty((N, L, K, U), dtype=torch.float32, device=dev)
         _check(
-            _lib.pointops_gather_neighbors(x.data_ptr(), idx.data_ptr(),
-                                           lengths.data_ptr() if lengths is not None else None,
-                                           N, M, U, L, K, out.data_ptr(), _stream()),
+            _lib.pointops_gather_neighbors(x.data_ptr(), idx.data_ptr(), _ptr(lengths), N, M, U, L, K,
+                                           out.data_ptr(), _stream()),
             "gather_neighbors",
         )
     return out
@@ -551,19 +533,17 @@ def gather_neighbors_backward(grad_out, idx, lengths, M: int, deterministic: boo
         grad_x = torch.empty((N, M, U), dtype=torch.float32, device=dev)
         if deterministic:  # inverted neighbour table: every row of x sums its addends in table order
             ws_bytes = _lib.pointops_backward_det_workspace_bytes(N, L, K, M)
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            ws = _workspace(ws_bytes, dev)
             _check(
                 _lib.pointops_gather_neighbors_backward_det(
-                    grad_out.data_ptr(), idx.data_ptr(), lengths.data_ptr() if lengths is not None else None,
-                    N, M, U, L, K, grad_x.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+                    grad_out.data_ptr(), idx.data_ptr(), _ptr(lengths),
+                    N, M, U, L, K, grad_x.data_ptr(), _ptr(ws), ws_bytes, _stream()),
                 "gather_neighbors_backward(deterministic)",
             )
             return grad_x
         _check(
-            _lib.pointops_gather_neighbors_backward(
-                grad_out.data_ptr(), idx.data_ptr(),
-                lengths.data_ptr() if lengths is not None else None, N, M, U, L, K,
-                grad_x.data_ptr(), _stream()),
+            _lib.pointops_gather_neighbors_backward(grad_out.data_ptr(), idx.data_ptr(), _ptr(lengths), N, M, U, L, K,
+                                                    grad_x.data_ptr(), _stream()),
             "gather_neighbors_backward",
         )
     return grad_x
@@ -580,9 +560,8 @@ def chamfer_reduce(dists, lengths, weights, mean: bool):
     with _on(dev):
         out = torch.empty((N,), dtype=torch.float32, device=dev)
         _check(
-            _lib.pointops_chamfer_reduce(dists.data_ptr(), lengths.data_ptr(),
-                                         weights.data_ptr() if weights is not None else None,
-                                         N, P, int(bool(mean)), out.data_ptr(), _stream()),
+            _lib.pointops_chamfer_reduce(dists.data_ptr(), lengths.data_ptr(), _ptr(weights), N, P, int(bool(mean)),
+                                         out.data_ptr(), _stream()),
             "chamfer_reduce",
         )
     return out
@@ -632,13 +611,12 @@ def chamfer_forward(dists, idx, x_lengths, y_lengths, weights, x_feats, y_feats,
     with _on(dev):
         out = torch.empty((1 + F, N), dtype=torch.float32, device=dev)
         ws_bytes = _lib.pointops_chamfer_workspace_bytes(N, P1)
-        ws = torch.empty((max(ws_bytes, 4),), dtype=torch.uint8, device=dev)
+        ws = _workspace(ws_bytes, dev)
         _check(
             _lib.pointops_chamfer_forward(dists.data_ptr(), idx.data_ptr(), x_lengths.data_ptr(),
-                                          y_lengths.data_ptr(),
-                                          weights.data_ptr() if weights is not None else None, N, P1, P2, F,
+                                          y_lengths.data_ptr(), _ptr(weights), N, P1, P2, F,
                                           _ptr_array(x_feats), _ptr_array(y_feats), C, int(bool(abs_cosine)),
-                                          int(bool(mean)), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+                                          int(bool(mean)), out.data_ptr(), _ptr(ws), ws_bytes, _stream()),
             "chamfer_forward",
         )
     return out
@@ -681,7 +659,7 @@ def chamfer_backward(x, y, idx, x_lengths, y_lengths, weights, grad_out, norm: i
             entry = _lib.pointops_chamfer_backward_accumulate
         _check(
             entry(x.data_ptr(), y.data_ptr(), idx.data_ptr(), x_lengths.data_ptr(), y_lengths.data_ptr(),
-                  weights.data_ptr() if weights is not None else None, grad_out.data_ptr(), N, P1, P2, D, int(norm),
+                  _ptr(weights), grad_out.data_ptr(), N, P1, P2, D, int(norm),
                   F, _ptr_array(x_feats), _ptr_array(y_feats), C, int(bool(abs_cosine)), int(bool(mean)),
                   grad_x.data_ptr(), grad_y.data_ptr(), _ptr_array(gxf), _ptr_array(gyf), _stream()),
             "chamfer_backward",
@@ -726,13 +704,12 @@ def chamfer_pair_forward(x, y, x_lengths, y_lengths, norm: int, x_feats, y_feats
         idx_yx = torch.empty((N, P2), dtype=torch.int64, device=dev)
         outs = [torch.empty(() if red else (N,), dtype=torch.float32, device=dev) for _ in range(1 + F)]
         ws_bytes = _lib.pointops_chamfer_pair_workspace_bytes(N, P1, P2, D, F)
-        ws = _scratch(ws_bytes, dev) if ws_bytes else None
+        ws = _workspace(ws_bytes, dev)
         _check(
             _lib.pointops_chamfer_pair_forward(x.data_ptr(), y.data_ptr(), x_lengths.data_ptr(), y_lengths.data_ptr(), N,
                                                P1, P2, D, int(norm), F, _ptr_array(x_feats), _ptr_array(y_feats), C,
                                                int(bool(abs_cosine)), int(bool(mean)), red, idx_xy.data_ptr(),
-                                               idx_yx.data_ptr(), _ptr_array(outs),
-                                               ws.data_ptr() if ws is not None else None, ws_bytes, _stream()),
+                                               idx_yx.data_ptr(), _ptr_array(outs), _ptr(ws), ws_bytes, _stream()),
             "chamfer_pair_forward",
         )
     return outs, idx_xy, idx_yx
@@ -761,13 +738,13 @@ def chamfer_pair_backward(x, y, idx_xy, idx_yx, x_lengths, y_lengths, grads, nor
         gxf = [torch.empty_like(t) for t in x_feats]
         gyf = [torch.empty_like(t) for t in y_feats]
         ws_bytes = 4 * (1 + F) * N
-        ws = _scratch(ws_bytes, dev)
+        ws = _workspace(ws_bytes, dev)
         _check(
             _lib.pointops_chamfer_pair_backward(x.data_ptr(), y.data_ptr(), idx_xy.data_ptr(), idx_yx.data_ptr(),
                                                 x_lengths.data_ptr(), y_lengths.data_ptr(), garr, N, P1, P2, D,
                                                 int(norm), F, _ptr_array(x_feats), _ptr_array(y_feats), C,
                                                 int(bool(abs_cosine)), int(bool(mean)), red, grad_x.data_ptr(),
-                                                grad_y.data_ptr(), _ptr_array(gxf), _ptr_array(gyf), ws.data_ptr(),
+                                                grad_y.data_ptr(), _ptr_array(gxf), _ptr_array(gyf), _ptr(ws),
                                                 ws_bytes, _stream()),
             "chamfer_pair_backward",
         )

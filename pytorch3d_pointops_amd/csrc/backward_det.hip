@@ -27,35 +27,30 @@ struct DetWs {
   size_t sort_tmp_bytes;
 };
 
-static inline size_t det_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int det_key_bits(int64_t targets) {  // keys 0 .. targets (targets = the slot of masked entries)
   int b = 1;
   while (((int64_t)1 << b) <= targets) ++b;
   return b;
 }
 
-static size_t det_carve(DetWs* ws, char* base, int64_t T, int64_t targets) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += det_align(bytes);
-    return p;
-  };
+// the table of N L K entries (at least one) keyed by the N M target rows
+static size_t det_carve(DetWs* ws, void* base, int64_t N, int64_t L, int64_t K, int64_t M) {
+  const int64_t T = N * L * K > 0 ? N * L * K : 1, targets = N * M;
+  Carver c(base);
   DetWs w;
-  w.keys_in = (unsigned*)take(sizeof(unsigned) * (size_t)T);
-  w.keys_out = (unsigned*)take(sizeof(unsigned) * (size_t)T);
-  w.vals_in = (unsigned*)take(sizeof(unsigned) * (size_t)T);
-  w.vals_out = (unsigned*)take(sizeof(unsigned) * (size_t)T);
-  w.seg_start = (int*)take(sizeof(int) * (size_t)(targets + 1));
-  w.seg_end = (int*)take(sizeof(int) * (size_t)(targets + 1));
+  w.keys_in = (unsigned*)c.take(sizeof(unsigned) * (size_t)T);
+  w.keys_out = (unsigned*)c.take(sizeof(unsigned) * (size_t)T);
+  w.vals_in = (unsigned*)c.take(sizeof(unsigned) * (size_t)T);
+  w.vals_out = (unsigned*)c.take(sizeof(unsigned) * (size_t)T);
+  w.seg_start = (int*)c.take(sizeof(int) * (size_t)(targets + 1));
+  w.seg_end = (int*)c.take(sizeof(int) * (size_t)(targets + 1));
   size_t tmp = 0;
   (void)rocprim::radix_sort_pairs(nullptr, tmp, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr,
                                   (unsigned*)nullptr, (size_t)T, 0, (unsigned)det_key_bits(targets), (hipStream_t)0);
   w.sort_tmp_bytes = tmp;
-  w.sort_tmp = take(tmp);
+  w.sort_tmp = c.take(tmp);
   if (ws) *ws = w;
-  return off;
+  return c.off;
 }
 
 // keys of the table entries: target row n M + idx, or `masked` (= N M) for entries the forward masks:
@@ -193,8 +188,7 @@ static int det_invert(const DetWs& ws, const int64_t* idx, const int64_t* length
 using namespace pointops;
 
 extern "C" size_t pointops_backward_det_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M) {
-  if (N <= 0 || M <= 0) return 256;
-  return det_carve(nullptr, nullptr, N * L * K > 0 ? N * L * K : 1, N * M);
+  return det_carve(nullptr, nullptr, N, L, K, M);
 }
 
 extern "C" int pointops_knn_points_backward_det(const float* p1, const float* p2, const int64_t* lengths1,
@@ -207,11 +201,10 @@ extern "C" int pointops_knn_points_backward_det(const float* p1, const float* p2
   POINTOPS_REQUIRE(N * P1 * K < (1LL << 31) && N * P2 < (1LL << 31) - 1 && N * P1 * D < (1LL << 40) && D < (1LL << 16),
                    "knn_points_backward(deterministic): the neighbour table must have fewer than 2^31 entries");
   if (N == 0) return POINTOPS_OK;
-  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= pointops_backward_det_workspace_bytes(N, P1, K, P2),
+  DetWs ws;
+  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, det_carve(&ws, workspace, N, P1, K, P2)),
                    "knn_points_backward(deterministic): workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
-  DetWs ws;
-  det_carve(&ws, (char*)workspace, N * P1 * K > 0 ? N * P1 * K : 1, N * P2);
   const int rc = det_invert(ws, idxs, lengths1, lengths2, N, P1, K, P2, stream);
   if (rc != POINTOPS_OK) return rc;
   if (N * P2 * D > 0) {
@@ -243,11 +236,10 @@ extern "C" int pointops_gather_neighbors_backward_det(const float* grad_out, con
   POINTOPS_REQUIRE(N * L * K < (1LL << 31) && N * M < (1LL << 31) - 1,
                    "gather_neighbors_backward(deterministic): the neighbour table must have fewer than 2^31 entries");
   if (N == 0 || M == 0) return POINTOPS_OK;
-  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= pointops_backward_det_workspace_bytes(N, L, K, M),
+  DetWs ws;
+  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, det_carve(&ws, workspace, N, L, K, M)),
                    "gather_neighbors_backward(deterministic): workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
-  DetWs ws;
-  det_carve(&ws, (char*)workspace, N * L * K > 0 ? N * L * K : 1, N * M);
   // knn_gather masks k >= lengths[n] (the lengths of the gathered cloud); queries have no lengths here
   const int rc = det_invert(ws, idx, nullptr, lengths, N, L, K, M, stream);
   if (rc != POINTOPS_OK) return rc;

@@ -9,6 +9,7 @@
 // the result is deterministic run to run.
 #include "common.h"
 #include "debug.h"
+#include "knn_grid.h"
 #include "zero_fill.h"
 
 namespace pointops {
@@ -346,12 +347,14 @@ __global__ __launch_bounds__(kCfBlock) void chamfer_backward4_kernel(
   }
 }
 
+// workgroups per cloud of chamfer_forward_kernel, one partial sum per term each (an empty cloud still takes one)
+static int cf_chunks(int64_t P1) { return (int)ceil_div(P1 > 0 ? P1 : 1, (int64_t)kCfBlock * kCfPerThread); }
+
 }  // namespace pointops
 
 extern "C" size_t pointops_chamfer_workspace_bytes(int64_t N, int64_t P1) {
   using namespace pointops;
-  const int64_t chunks = ceil_div(P1 > 0 ? P1 : 1, (int64_t)kCfBlock * kCfPerThread);
-  return sizeof(float) * (size_t)(N * chunks * (1 + kCfMaxFeat));
+  return sizeof(float) * (size_t)(N * cf_chunks(P1) * (1 + kCfMaxFeat));
 }
 
 static int cf_fill(pointops::ChamferFeat* ft, int F, const float* const* xf, const float* const* yf,
@@ -381,10 +384,10 @@ extern "C" int pointops_chamfer_forward(const float* dists, const int64_t* idx, 
   ChamferFeat ft;
   const int rc = cf_fill(&ft, F, x_feats, y_feats, nullptr, nullptr, C);
   if (rc != POINTOPS_OK) return rc;
-  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= pointops_chamfer_workspace_bytes(N, P1),
+  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, pointops_chamfer_workspace_bytes(N, P1)),
                    "chamfer_forward: workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
-  const int chunks = (int)ceil_div(P1 > 0 ? P1 : 1, (int64_t)kCfBlock * kCfPerThread);
+  const int chunks = cf_chunks(P1);
   hipLaunchKernelGGL(chamfer_forward_kernel, dim3((unsigned)chunks, (unsigned)N), dim3(kCfBlock), 0, stream, dists,
                      idx, x_lengths, y_lengths, P1, P2, ft, abs_cosine, chunks, (float*)workspace);
   hipLaunchKernelGGL(chamfer_finalize_kernel, dim3((unsigned)N), dim3(kWave), 0, stream, (const float*)workspace,
@@ -465,8 +468,6 @@ extern "C" int pointops_chamfer_backward_accumulate(const float* x, const float*
 // ===========================================================================
 namespace pointops {
 
-__host__ __device__ inline size_t cp_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // rows = rows_a + rows_b, (1+F, N); reduce: 0 none -> out (1+F, N); 1 mean, 2 sum over the batch -> out (1+F)
 struct PairOuts {
   float* o[1 + kCfMaxFeat];  // one tensor per output: (N,) without a batch reduction, () with one
@@ -536,15 +537,35 @@ static PairSide* pair_side() {  // per host thread and device; created on first 
   return s;
 }
 
-extern "C" size_t pointops_chamfer_pair_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D, int F) {
+// both searches' workspaces (laid out for two concurrent searches whether or not they overlap) and distances, the
+// partial sums of chamfer_forward (one direction after the other) and each direction's (1+F, N) terms
+struct PairWs {
+  void *knn_a, *knn_b, *ch;
+  size_t knn_a_bytes, knn_b_bytes, ch_bytes;
+  float *dists_a, *dists_b, *rows_a, *rows_b;
+};
+
+static size_t pair_carve(PairWs* ws, void* base, int64_t N, int64_t P1, int64_t P2, int64_t D, int F) {
   using namespace pointops;
-  if (N <= 0) return 0;
-  const size_t knn_a = pointops_knn_workspace_bytes(N, P1, P2, D, 1, -1), knn_b = pointops_knn_workspace_bytes(N, P2, P1, D, 1, -1);
+  Carver c(base);
+  PairWs w;
+  w.knn_a_bytes = knn_plan(N, P1, P2, D, 1, -1).workspace_bytes;
+  w.knn_b_bytes = knn_plan(N, P2, P1, D, 1, -1).workspace_bytes;
   const size_t ch_a = pointops_chamfer_workspace_bytes(N, P1), ch_b = pointops_chamfer_workspace_bytes(N, P2);
-  // (laid out for two concurrent searches whether or not they overlap)
-  return cp_align(knn_a) + cp_align(knn_b) + cp_align(sizeof(float) * (size_t)(N * P1)) +
-         cp_align(sizeof(float) * (size_t)(N * P2)) + cp_align(ch_a > ch_b ? ch_a : ch_b) +
-         2 * cp_align(sizeof(float) * (size_t)((1 + F) * N));
+  w.ch_bytes = ch_a > ch_b ? ch_a : ch_b;
+  w.knn_a = c.take(w.knn_a_bytes);
+  w.knn_b = c.take(w.knn_b_bytes);
+  w.dists_a = (float*)c.take(sizeof(float) * (size_t)(N * P1));
+  w.dists_b = (float*)c.take(sizeof(float) * (size_t)(N * P2));
+  w.ch = c.take(w.ch_bytes);
+  w.rows_a = (float*)c.take(sizeof(float) * (size_t)((1 + F) * N));
+  w.rows_b = (float*)c.take(sizeof(float) * (size_t)((1 + F) * N));
+  if (ws) *ws = w;
+  return c.off;
+}
+
+extern "C" size_t pointops_chamfer_pair_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D, int F) {
+  return pair_carve(nullptr, nullptr, N, P1, P2, D, F);
 }
 
 extern "C" int pointops_chamfer_pair_forward(const float* x, const float* y, const int64_t* x_lengths,
@@ -558,25 +579,10 @@ extern "C" int pointops_chamfer_pair_forward(const float* x, const float* y, con
   POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && D >= 1 && N < 65536 && F >= 0 && F <= kCfMaxFeat,
                    "chamfer_pair_forward: bad sizes");
   POINTOPS_REQUIRE(batch_reduction >= 0 && batch_reduction <= 2, "chamfer_pair_forward: batch_reduction must be 0, 1 or 2");
-  if (N == 0) return POINTOPS_OK;
-  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= pointops_chamfer_pair_workspace_bytes(N, P1, P2, D, F),
+  // (N = 0 runs through: the searches and reductions return at once, the combine writes 0 after a batch reduction)
+  PairWs ws;
+  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, pair_carve(&ws, workspace, N, P1, P2, D, F)),
                    "chamfer_pair_forward: workspace too small");
-  const size_t knn_a = pointops_knn_workspace_bytes(N, P1, P2, D, 1, -1), knn_b = pointops_knn_workspace_bytes(N, P2, P1, D, 1, -1);
-  const size_t ch_a = pointops_chamfer_workspace_bytes(N, P1), ch_b = pointops_chamfer_workspace_bytes(N, P2);
-  char* w = (char*)workspace;
-  void* knn_ws_a = w;
-  w += cp_align(knn_a);
-  void* knn_ws_b = w;
-  w += cp_align(knn_b);
-  float* dists_a = (float*)w;
-  w += cp_align(sizeof(float) * (size_t)(N * P1));
-  float* dists_b = (float*)w;
-  w += cp_align(sizeof(float) * (size_t)(N * P2));
-  void* ch_ws = w;
-  w += cp_align(ch_a > ch_b ? ch_a : ch_b);
-  float* rows_a = (float*)w;
-  w += cp_align(sizeof(float) * (size_t)((1 + F) * N));
-  float* rows_b = (float*)w;
   hipStream_t main_stream = (hipStream_t)stream_;
   PairSide* side = pair_overlap(N, P1, P2, D) ? pair_side() : nullptr;
   void* stream_b = stream_;
@@ -586,27 +592,27 @@ extern "C" int pointops_chamfer_pair_forward(const float* x, const float* y, con
     stream_b = (void*)side->stream;
   }
   // the reverse search first: on its own stream it overlaps everything the forward direction does
-  int rc = pointops_knn_points_idx(y, x, y_lengths, x_lengths, N, P2, P1, D, norm, 1, -1, idx_yx, dists_b, knn_ws_b, knn_b,
-                                   stream_b);
+  int rc = pointops_knn_points_idx(y, x, y_lengths, x_lengths, N, P2, P1, D, norm, 1, -1, idx_yx, ws.dists_b, ws.knn_b,
+                                   ws.knn_b_bytes, stream_b);
   if (side != nullptr && hipEventRecord(side->join, side->stream) != hipSuccess) rc = check_launch("chamfer_pair_forward(join)");
   const int rc_b = rc;
-  rc = pointops_knn_points_idx(x, y, x_lengths, y_lengths, N, P1, P2, D, norm, 1, -1, idx_xy, dists_a, knn_ws_a, knn_a,
-                               stream_);
+  rc = pointops_knn_points_idx(x, y, x_lengths, y_lengths, N, P1, P2, D, norm, 1, -1, idx_xy, ws.dists_a, ws.knn_a,
+                               ws.knn_a_bytes, stream_);
   if (rc == POINTOPS_OK)
-    rc = pointops_chamfer_forward(dists_a, idx_xy, x_lengths, y_lengths, nullptr, N, P1, P2, F, x_feats, y_feats, C,
-                                  abs_cosine, mean, rows_a, ch_ws, ch_a, stream_);
+    rc = pointops_chamfer_forward(ws.dists_a, idx_xy, x_lengths, y_lengths, nullptr, N, P1, P2, F, x_feats, y_feats, C,
+                                  abs_cosine, mean, ws.rows_a, ws.ch, ws.ch_bytes, stream_);
   // join before anything else can fail out: the caller's stream must not run ahead of the side stream's use of the workspace
   if (side != nullptr && hipStreamWaitEvent(main_stream, side->join, 0) != hipSuccess)
     return check_launch("chamfer_pair_forward(join)");
   if (rc_b != POINTOPS_OK) return rc_b;
   if (rc != POINTOPS_OK) return rc;
-  rc = pointops_chamfer_forward(dists_b, idx_yx, y_lengths, x_lengths, nullptr, N, P2, P1, F, y_feats, x_feats, C,
-                                abs_cosine, mean, rows_b, ch_ws, ch_b, stream_);
+  rc = pointops_chamfer_forward(ws.dists_b, idx_yx, y_lengths, x_lengths, nullptr, N, P2, P1, F, y_feats, x_feats, C,
+                                abs_cosine, mean, ws.rows_b, ws.ch, ws.ch_bytes, stream_);
   if (rc != POINTOPS_OK) return rc;
   PairOuts po;
   for (int f = 0; f < 1 + kCfMaxFeat; ++f) po.o[f] = f <= F ? outs[f] : nullptr;
-  hipLaunchKernelGGL(chamfer_pair_combine_kernel, dim3((unsigned)(1 + F)), dim3(kWave), 0, (hipStream_t)stream_, rows_a,
-                     rows_b, (int)N, batch_reduction, po);
+  hipLaunchKernelGGL(chamfer_pair_combine_kernel, dim3((unsigned)(1 + F)), dim3(kWave), 0, (hipStream_t)stream_,
+                     ws.rows_a, ws.rows_b, (int)N, batch_reduction, po);
   return check_launch("chamfer_pair_forward");
 }
 

@@ -29,6 +29,24 @@ inline int check_launch(const char* what) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Lays a workspace out as consecutive 256-byte aligned arrays.  With a null base it only sizes (take() returns null):
+// one layout function serves both an operator's *_workspace_bytes query and its entry.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base((char*)b) {}
+  char* take(size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  }
+};
+
+// a caller's workspace of `bytes` holds a layout of `need` bytes (null only when nothing is needed)
+inline bool workspace_fits(const void* ws, size_t bytes, size_t need) {
+  return bytes >= need && (ws != nullptr || need == 0);
+}
+
 }  // namespace pointops
 
 #define POINTOPS_REQUIRE(cond, ...)        \

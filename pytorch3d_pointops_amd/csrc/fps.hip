@@ -570,12 +570,11 @@ static int fps_num_cus() {
 // Not beyond that: two workgroups per CU (the <3, 4> kernel held to 64 VGPRs) do not overlap each other's latency
 // (16 x 131072: 1.51 -> 1.73 ms), and a cloud that fits one workgroup is fastest without an exchange (64 x 8192 -> 256:
 // 0.26 against 0.33 ms).  tools/fps_plan_sweep.py, profiles/r03_fps_plan_sweep.txt.
-// D <= 0: the plan with the most workgroups per cloud any D could take (workspace sizing).
 static void fps_plan(int64_t N, int64_t P, int64_t D, int* ppt, int* G) {
   const int cus = fps_num_cus();
   int p = P <= 8 * (int64_t)kFpsBlock * cus ? 8 : 16;
   if (P <= 4 * (int64_t)kFpsBlock) p = 4;
-  if (p == 8 && (D == 3 || D <= 0) && debug_knob("fps_small_ppt", 1) != 0) {
+  if (p == 8 && D == 3 && debug_knob("fps_small_ppt", 1) != 0) {
     const int64_t g4 = ceil_div(P, (int64_t)4 * kFpsBlock);
     if (P > 8 * (int64_t)kFpsBlock && N * g4 <= (int64_t)cus && g4 <= (int64_t)cus / 8) p = 4;
   }
@@ -597,18 +596,34 @@ static int fps_resident_blocks(Kernel kernel) {
   return fps_num_cus() * (per_cu > 1 ? 1 : per_cu);  // one 1024-lane workgroup per CU is what the plan uses
 }
 
-static size_t fps_slot_bytes(int64_t N, int64_t max_K, int G) {
-  return sizeof(unsigned long long) * (size_t)(N * max_K) * (size_t)(G > 1 ? G : 1);
+// workgroups per cloud of the plan for the worst D (the size query has no D): only D = 3 may take fewer points per lane
+static int fps_max_groups(int64_t N, int64_t P) {
+  int ppt, G;
+  fps_plan(N, P, 3, &ppt, &G);
+  return G;
+}
+
+struct FpsWs {
+  float* min_dist;            // v1 running min-distance array (N*P floats)
+  unsigned long long* slots;  // v2 exchange rows: one u64 slot per (cloud, iteration, cluster member), directly
+  unsigned* timeout_flags;    // followed by one timeout word per cloud (zeroed together)
+  size_t slot_bytes;
+};
+
+static size_t fps_carve(FpsWs* ws, void* base, int64_t N, int64_t P, int64_t max_K, int G) {
+  Carver c(base);
+  FpsWs w;
+  w.slot_bytes = sizeof(unsigned long long) * (size_t)(N * max_K) * (size_t)(G > 1 ? G : 1);
+  w.min_dist = (float*)c.take(sizeof(float) * (size_t)(N * P));
+  char* ex = c.take(w.slot_bytes + sizeof(unsigned) * (size_t)N + 64);
+  w.slots = (unsigned long long*)ex;
+  w.timeout_flags = (unsigned*)(ex ? ex + w.slot_bytes : nullptr);
+  if (ws) *ws = w;
+  return c.off;
 }
 
 extern "C" size_t pointops_fps_workspace_bytes(int64_t N, int64_t P, int64_t max_K) {
-  // v1 running min-distance array (N*P floats) + v2 exchange rows: one u64 slot per
-  // (cloud, iteration, cluster member) + one timeout word per cloud
-  int ppt, G;
-  fps_plan(N, P, 0, &ppt, &G);
-  const size_t md = sizeof(float) * (size_t)(N * P);
-  const size_t ex = fps_slot_bytes(N, max_K, G) + sizeof(unsigned) * (size_t)N + 64;
-  return ((md + 255) & ~(size_t)255) + ex;
+  return fps_carve(nullptr, nullptr, N, P, max_K, fps_max_groups(N, P));
 }
 
 extern "C" int pointops_sample_farthest_points(const float* points, const int64_t* lengths,
@@ -620,21 +635,18 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
   POINTOPS_REQUIRE(P < (1LL << 31) && max_K < (1LL << 31) && D < (1LL << 16) && N < (1LL << 31),
                    "sample_farthest_points: sizes must fit int32");
   if (N == 0 || max_K == 0) return POINTOPS_OK;
-  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= pointops_fps_workspace_bytes(N, P, max_K),
-                   "sample_farthest_points: workspace of %zu bytes required",
-                   pointops_fps_workspace_bytes(N, P, max_K));
-  hipStream_t stream = (hipStream_t)stream_;
-  float* min_dist_ws = (float*)workspace;
-  char* ex = (char*)workspace + ((sizeof(float) * (size_t)(N * P) + 255) & ~(size_t)255);
+  const size_t need = pointops_fps_workspace_bytes(N, P, max_K);
+  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, need),
+                   "sample_farthest_points: workspace of %zu bytes required", need);
   int ppt, G;
   fps_plan(N, P, D, &ppt, &G);
-  const size_t slot_bytes = fps_slot_bytes(N, max_K, G);
-  unsigned long long* slots = (unsigned long long*)ex;
-  unsigned* timeout_flags = (unsigned*)(ex + slot_bytes);
+  FpsWs ws;
+  fps_carve(&ws, workspace, N, P, max_K, G);
+  hipStream_t stream = (hipStream_t)stream_;
 
 #define PO_LAUNCH(DT, FLAGS)                                                                      \
   hipLaunchKernelGGL((fps_kernel<DT>), dim3((unsigned)N), dim3(kFpsBlock), 0, stream, points, lengths, K, \
-                     start_idxs, (int)P, (int)D, (int)max_K, idxs, min_dist_ws, FLAGS)
+                     start_idxs, (int)P, (int)D, (int)max_K, idxs, ws.min_dist, FLAGS)
   // small clouds: one four-wave workgroup per cloud
   if ((D == 3 || D == 2) && P >= 1 && P <= 16 * kFpsSmallBlock && debug_knob("fps_small", 1) != 0) {
 #define PO_SMALL(DT, PPT)                                                                                          \
@@ -678,7 +690,8 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
         mode = 0;
       }
       if (G > 1) {
-        const int zrc = zero_words_async(ex, (int64_t)(slot_bytes / sizeof(unsigned)) + N, stream, "fps(zero)");
+        const int64_t words = (int64_t)(ws.slot_bytes / sizeof(unsigned)) + N;  // the slots and the timeout words
+        const int zrc = zero_words_async(ws.slots, words, stream, "fps(zero)");
         if (zrc != POINTOPS_OK) return zrc;
       }
       // XCD-local numbering: cluster c = (j / G) * 8 + x for the j-th block of XCD group x
@@ -687,7 +700,7 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
       const dim3 grid((unsigned)blocks), block(kFpsBlock);
 #define PO_LAUNCH_C(DT, PPT)                                                                         \
   hipLaunchKernelGGL((fps_cluster_kernel<DT, PPT>), grid, block, 0, stream, points, lengths, K, start_idxs, \
-                     (int)N, (int)P, (int)max_K, G, n_clusters, mode, spin_limit, slots, timeout_flags, idxs)
+                     (int)N, (int)P, (int)max_K, G, n_clusters, mode, spin_limit, ws.slots, ws.timeout_flags, idxs)
       if (D == 3) {
         if (ppt == 4) PO_LAUNCH_C(3, 4);
         else if (ppt == 8) PO_LAUNCH_C(3, 8);
@@ -702,8 +715,8 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
       if (rc != POINTOPS_OK || G == 1) return rc;
       // repair pass: clouds whose exchange timed out (CUs taken away by another kernel or a CU mask) are
       // redone by the single-workgroup kernel; a cloud that was not flagged returns at once
-      if (D == 3) PO_LAUNCH(3, (const unsigned*)timeout_flags);
-      else PO_LAUNCH(2, (const unsigned*)timeout_flags);
+      if (D == 3) PO_LAUNCH(3, (const unsigned*)ws.timeout_flags);
+      else PO_LAUNCH(2, (const unsigned*)ws.timeout_flags);
       return check_launch("sample_farthest_points(repair)");
     }
   }

@@ -820,8 +820,6 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int grid_cell_cap(int64_t P2, float c_target) {
   const int64_t cells = (int64_t)ceil((double)P2 / (double)c_target);
   return (int)(2 * cells + 64);
@@ -829,58 +827,53 @@ static int grid_cell_cap(int64_t P2, float c_target) {
 
 size_t grid_carve(GridWs* ws, char* base, int64_t N, int64_t P1, int64_t P2, float c, bool ball) {
   const int cap = grid_cell_cap(P2, c);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes);
-    return p;
-  };
+  Carver cv(base);
   GridWs w;
   w.cell_cap = cap;
-  w.cloud = (GridCloud*)take(sizeof(GridCloud) * (size_t)N);
-  w.chunk_prefix = (int*)take(sizeof(int) * (size_t)(N + 1));
-  w.edges = (float*)take(sizeof(float) * (size_t)N * 3 * kEdgeStride);
-  w.cell_start = (int*)take(sizeof(int) * (size_t)N * (cap + 1));
-  w.coarse_count = (int*)take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
-  w.coarse_cursor = (int*)take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
-  w.coarse_start = (int*)take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
-  w.bin_of = (int*)take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
-  w.bin_first = (int*)take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
-  w.nbins = (int*)take(sizeof(int) * (size_t)N * 2);
-  w.coarse_ticket = (int*)take(sizeof(int) * (size_t)N * 2);
-  w.crowded_count = (int*)take(sizeof(int) * (size_t)N * 2);
-  w.crowded_list = (int*)take(sizeof(int) * (size_t)N * 2 * kCrowdedMax);
-  w.fine_count = (int*)take(sizeof(int) * (size_t)N * 2 * cap);
-  w.prank = (int*)take(sizeof(int) * (size_t)N * (size_t)P2);
-  w.qrank = (int*)take(sizeof(int) * (size_t)N * (size_t)P1);
-  w.order_table = (int*)take(ball ? sizeof(int) * (size_t)N * (size_t)((P1 + 2047) / 2048) * kOrderBins : 0);
-  w.sorted = (float4*)take(sizeof(float4) * (size_t)N * (size_t)(P2 + kSortedPad));
-  w.qsorted = (float4*)take(sizeof(float4) * (size_t)N * (size_t)P1);
-  w.fb_count = (int*)take(sizeof(int) * (size_t)N);
-  w.fb_list = (int*)take(sizeof(int) * (size_t)N * (size_t)P1);
-  w.fb_kth = (unsigned*)take(sizeof(unsigned) * (size_t)N * (size_t)P1);
-  w.fb2_count = (int*)take(sizeof(int) * (size_t)N);
-  w.fb2_list = (int*)take(sizeof(int) * (size_t)N * (size_t)P1);
-  w.fb3_count = (int*)take(sizeof(int) * (size_t)N);
-  w.fb3_list = (int*)take(sizeof(int) * (size_t)N * (size_t)P1);
-  w.bbox = (unsigned*)take(sizeof(unsigned) * (size_t)N * 8);
-  w.bbox_part = (float*)take(sizeof(float) * (size_t)N * 6 * (size_t)((P2 + 2047) / 2048));
-  w.grid_flag = (int*)take(sizeof(int) * (size_t)N);
-  w.qtmp = (float4*)take(sizeof(float4) * (size_t)N * (size_t)P1);
+  w.cloud = (GridCloud*)cv.take(sizeof(GridCloud) * (size_t)N);
+  w.chunk_prefix = (int*)cv.take(sizeof(int) * (size_t)(N + 1));
+  w.edges = (float*)cv.take(sizeof(float) * (size_t)N * 3 * kEdgeStride);
+  w.cell_start = (int*)cv.take(sizeof(int) * (size_t)N * (cap + 1));
+  w.coarse_count = (int*)cv.take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
+  w.coarse_cursor = (int*)cv.take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
+  w.coarse_start = (int*)cv.take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
+  w.bin_of = (int*)cv.take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
+  w.bin_first = (int*)cv.take(sizeof(int) * (size_t)N * 2 * (kCoarseMax + 1));
+  w.nbins = (int*)cv.take(sizeof(int) * (size_t)N * 2);
+  w.coarse_ticket = (int*)cv.take(sizeof(int) * (size_t)N * 2);
+  w.crowded_count = (int*)cv.take(sizeof(int) * (size_t)N * 2);
+  w.crowded_list = (int*)cv.take(sizeof(int) * (size_t)N * 2 * kCrowdedMax);
+  w.fine_count = (int*)cv.take(sizeof(int) * (size_t)N * 2 * cap);
+  w.prank = (int*)cv.take(sizeof(int) * (size_t)N * (size_t)P2);
+  w.qrank = (int*)cv.take(sizeof(int) * (size_t)N * (size_t)P1);
+  w.order_table = (int*)cv.take(ball ? sizeof(int) * (size_t)N * (size_t)((P1 + 2047) / 2048) * kOrderBins : 0);
+  w.sorted = (float4*)cv.take(sizeof(float4) * (size_t)N * (size_t)(P2 + kSortedPad));
+  w.qsorted = (float4*)cv.take(sizeof(float4) * (size_t)N * (size_t)P1);
+  w.fb_count = (int*)cv.take(sizeof(int) * (size_t)N);
+  w.fb_list = (int*)cv.take(sizeof(int) * (size_t)N * (size_t)P1);
+  w.fb_kth = (unsigned*)cv.take(sizeof(unsigned) * (size_t)N * (size_t)P1);
+  w.fb2_count = (int*)cv.take(sizeof(int) * (size_t)N);
+  w.fb2_list = (int*)cv.take(sizeof(int) * (size_t)N * (size_t)P1);
+  w.fb3_count = (int*)cv.take(sizeof(int) * (size_t)N);
+  w.fb3_list = (int*)cv.take(sizeof(int) * (size_t)N * (size_t)P1);
+  w.bbox = (unsigned*)cv.take(sizeof(unsigned) * (size_t)N * 8);
+  w.bbox_part = (float*)cv.take(sizeof(float) * (size_t)N * 6 * (size_t)((P2 + 2047) / 2048));
+  w.grid_flag = (int*)cv.take(sizeof(int) * (size_t)N);
+  w.qtmp = (float4*)cv.take(sizeof(float4) * (size_t)N * (size_t)P1);
   w.rdesc_cap = (int)(P2 / 64 + 1);  // a refined cell holds more than refine_threshold() >= 64 points
   w.pool_cap = (int)(4 * P2 + 64);   // sum of (s^3 + 1) <= sum of (8 count / c + 9) over refined cells
-  w.refine_ref = (int*)take(sizeof(int) * (size_t)N * cap);
-  w.rdesc = (RefinedCell*)take(sizeof(RefinedCell) * (size_t)N * (size_t)w.rdesc_cap);
-  w.rcount = (int*)take(sizeof(int) * (size_t)N);
-  w.pool = (int*)take(sizeof(int) * (size_t)N * (size_t)w.pool_cap);
-  w.pool_top = (int*)take(sizeof(int) * (size_t)N);
-  w.sorted_tmp = (float4*)take(sizeof(float4) * (size_t)N * (size_t)P2);
-  w.box_count = (int*)take(sizeof(int) * (size_t)N);
-  w.box_list = (int*)take(sizeof(int) * (size_t)N * (size_t)P1);
+  w.refine_ref = (int*)cv.take(sizeof(int) * (size_t)N * cap);
+  w.rdesc = (RefinedCell*)cv.take(sizeof(RefinedCell) * (size_t)N * (size_t)w.rdesc_cap);
+  w.rcount = (int*)cv.take(sizeof(int) * (size_t)N);
+  w.pool = (int*)cv.take(sizeof(int) * (size_t)N * (size_t)w.pool_cap);
+  w.pool_top = (int*)cv.take(sizeof(int) * (size_t)N);
+  w.sorted_tmp = (float4*)cv.take(sizeof(float4) * (size_t)N * (size_t)P2);
+  w.box_count = (int*)cv.take(sizeof(int) * (size_t)N);
+  w.box_list = (int*)cv.take(sizeof(int) * (size_t)N * (size_t)P1);
   w.c_target = c;
   w.ball = 0;
   if (ws) *ws = w;
-  return off;
+  return cv.off;
 }
 
 // sets: 0 = points only (self-query), 1 = queries only (the point side is already built: grid_build_queries), 2 = both

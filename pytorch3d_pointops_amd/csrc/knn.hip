@@ -212,7 +212,8 @@ static void dispatch_d(const KnnArgs& a, const RegLaunch& r) {
   }
 }
 
-int knn_split_count(int64_t N, int64_t P1, int64_t P2, int64_t K) {
+// p2 slices per query so that a small batch still fills the chip (1024 SIMDs)
+static int knn_split_count(int64_t N, int64_t P1, int64_t P2, int64_t K) {
   if (K > 32) return 1;
   const int64_t waves = N * ceil_div(P1, 64);
   if (waves >= 2048 || P2 < 512) return 1;
@@ -221,11 +222,6 @@ int knn_split_count(int64_t N, int64_t P1, int64_t P2, int64_t K) {
   s = std::min<int64_t>(s, P2 / 128);  // a slice keeps >= 128 candidates (cfg1, B=2 N=M=1024 K=8, us per call by (max
                                        // slices, candidates): (8, 256) 48.6, (8, 128) 37.5, (16, 64) 41.4, (32, 32) 56.0)
   return (int)std::max<int64_t>(s, 1);
-}
-
-size_t knn_split_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t K) {
-  const int S = knn_split_count(N, P1, P2, K);
-  return S > 1 ? sizeof(unsigned long long) * (size_t)(N * P1 * S * K) : 0;
 }
 
 void knn_merge_partials(const KnnArgs& a, int S, const void* workspace) {
@@ -246,41 +242,19 @@ void knn_merge_partials(const KnnArgs& a, int S, const void* workspace) {
 #undef PO_MERGE
 }
 
-void launch_knn_bruteforce(const KnnArgs& a, int norm, void* workspace) {
+void launch_knn_bruteforce(const KnnArgs& a, int norm, int splits, void* workspace) {
   // small batches: 64-lane workgroups (4x as many) and p2 slices; the query-list mode of the grid
   // fallback always scans whole clouds
   RegLaunch r{kKnnBlock, a.tiles, 1, nullptr};
   if (a.qlist == nullptr && a.N * a.tiles < 2048) {
     r.block = 64;
     r.tiles = (int)ceil_div(a.P1, 64);
-    if (workspace != nullptr) {
-      r.S = knn_split_count(a.N, a.P1, a.P2, a.K);
-      r.partial = (unsigned long long*)workspace;
-    }
+    r.S = splits;
+    r.partial = (unsigned long long*)workspace;
   }
   if (norm == 1) dispatch_d<1>(a, r);
   else dispatch_d<2>(a, r);
   if (r.S > 1) knn_merge_partials(a, r.S, workspace);
-}
-
-}  // namespace pointops
-
-using namespace pointops;
-
-extern "C" {
-
-int pointops_knn_check_version(int version, int64_t D, int64_t K) {
-  // Kernel families of this library.  As in the reference (csrc/knn/knn.cu:292-312) the
-  // highest valid version is the fastest and `version` never changes results:
-  //   0 any D, any K: LDS-transposed queries with register (K <= 32) or LDS lists (knn_wide.hip);
-  //     beyond the LDS budget the plain generic kernel (list kept in the output rows)
-  //   1, 2 register top-K brute-force scan (D in [1,8], K in [1,32])
-  //   3 exact grid-pruned search + brute-force fallback (D in [1,3], K in [1,128]: lane-private lists up to 64,
-  //     wave-per-query sorting above)
-  if (version == 0) return 1;
-  if (version == 1 || version == 2) return (D >= 1 && D <= 8 && K >= 1 && K <= 32) ? 1 : 0;
-  if (version == 3) return (D >= 1 && D <= 3 && K >= 1 && K <= 128) ? 1 : 0;
-  return 0;
 }
 
 static int choose_version(int version, int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K) {
@@ -305,14 +279,42 @@ static int choose_version(int version, int64_t N, int64_t P1, int64_t P2, int64_
   return 0;
 }
 
+KnnPlan knn_plan(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K, int version) {
+  if (N <= 0 || P1 <= 0 || D < 1 || K < 1) return {KnnFamily::kNone, 1, 0};
+  const int v = choose_version(version, N, P1, P2, D, K);
+  if (v == 3) return {KnnFamily::kGrid, 1, knn_grid_workspace_bytes(N, P1, P2, K)};
+  // v = 0, any D / long lists: LDS-transposed queries (POINTOPS_DEBUG knn_generic=1 keeps the plain kernel, tests);
+  // v = 1, 2: few queries take one wave per query (knn_small.hip), the others the register scan
+  if (v == 0 && !(knn_wide_supported(D, K) && debug_knob("knn_generic", 0) == 0)) return {KnnFamily::kGeneric, 1, 0};
+  if (v != 0 && knn_small_applies(N, P1, P2, D, K)) return {KnnFamily::kSmall, 1, 0};
+  const int S = knn_split_count(N, P1, P2, K);
+  const size_t partials = S > 1 ? sizeof(unsigned long long) * (size_t)(N * P1 * S * K) : 0;
+  return {v == 0 ? KnnFamily::kWide : KnnFamily::kScan, S, partials};
+}
+
+}  // namespace pointops
+
+using namespace pointops;
+
+extern "C" {
+
+int pointops_knn_check_version(int version, int64_t D, int64_t K) {
+  // Kernel families of this library.  As in the reference (csrc/knn/knn.cu:292-312) the
+  // highest valid version is the fastest and `version` never changes results:
+  //   0 any D, any K: LDS-transposed queries with register (K <= 32) or LDS lists (knn_wide.hip);
+  //     beyond the LDS budget the plain generic kernel (list kept in the output rows)
+  //   1, 2 register top-K brute-force scan (D in [1,8], K in [1,32])
+  //   3 exact grid-pruned search + brute-force fallback (D in [1,3], K in [1,128]: lane-private lists up to 64,
+  //     wave-per-query sorting above)
+  if (version == 0) return 1;
+  if (version == 1 || version == 2) return (D >= 1 && D <= 8 && K >= 1 && K <= 32) ? 1 : 0;
+  if (version == 3) return (D >= 1 && D <= 3 && K >= 1 && K <= 128) ? 1 : 0;
+  return 0;
+}
+
 size_t pointops_knn_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K,
                                     int version) {
-  if (N <= 0 || P1 <= 0 || D < 1 || K < 1) return 0;
-  const int v = choose_version(version, N, P1, P2, D, K);
-  if (v == 0 && !knn_wide_supported(D, K)) return 0;
-  if ((v == 1 || v == 2) && knn_small_applies(N, P1, P2, D, K)) return 0;
-  if (v != 3) return knn_split_workspace_bytes(N, P1, P2, K);
-  return knn_grid_workspace_bytes(N, P1, P2, K);
+  return knn_plan(N, P1, P2, D, K, version).workspace_bytes;
 }
 
 int pointops_knn_points_idx(const float* p1, const float* p2, const int64_t* lengths1,
@@ -324,8 +326,7 @@ int pointops_knn_points_idx(const float* p1, const float* p2, const int64_t* len
 }
 
 int pointops_knn_uses_grid(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K, int version) {
-  if (N <= 0 || P1 <= 0 || D < 1 || K < 1) return 0;
-  return choose_version(version, N, P1, P2, D, K) == 3 ? 1 : 0;
+  return knn_plan(N, P1, P2, D, K, version).family == KnnFamily::kGrid ? 1 : 0;
 }
 
 int pointops_knn_points_idx_reuse(const float* p1, const float* p2, const int64_t* lengths1,
@@ -350,38 +351,29 @@ int pointops_knn_points_idx_reuse(const float* p1, const float* p2, const int64_
   a.idxs = idxs; a.dists = dists; a.stream = (hipStream_t)stream;
   POINTOPS_REQUIRE(N * a.tiles < (1LL << 31), "knn_points_idx: grid too large");
 
-  const int v = choose_version(version, N, P1, P2, D, K);
-  if (v == 3) {
-    const size_t need = knn_grid_workspace_bytes(N, P1, P2, K);
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("knn_points_idx: workspace of %zu bytes required (got %zu)", need, workspace_bytes);
-      return POINTOPS_EWORKSPACE;
-    }
-    const int rc = knn_grid_run(a, norm, workspace, reuse);
-    if (rc != POINTOPS_OK) return rc;
-  } else if (v == 0 && knn_wide_supported(D, K) && debug_knob("knn_generic", 0) == 0) {
-    // any D / long lists: LDS-transposed queries (POINTOPS_KNN_GENERIC=1 keeps the plain fallback, tests)
-    const size_t need = knn_split_workspace_bytes(N, P1, P2, K);
-    if (need > 0 && (workspace == nullptr || workspace_bytes < need)) {
-      set_error("knn_points_idx: workspace of %zu bytes required (got %zu)", need, workspace_bytes);
-      return POINTOPS_EWORKSPACE;
-    }
-    const int rc = launch_knn_wide(a, norm, workspace);
-    if (rc != POINTOPS_OK) return rc;
-  } else if (v == 0) {
-    const dim3 grid((unsigned)(N * a.tiles));
-    if (norm == 1)
-      hipLaunchKernelGGL(knn_generic_kernel<1>, grid, dim3(kKnnBlock), 0, a.stream, p1, p2, lengths1,
-                         lengths2, a.P1, a.P2, a.D, a.K, a.tiles, idxs, dists);
-    else
-      hipLaunchKernelGGL(knn_generic_kernel<2>, grid, dim3(kKnnBlock), 0, a.stream, p1, p2, lengths1,
-                         lengths2, a.P1, a.P2, a.D, a.K, a.tiles, idxs, dists);
-  } else if (knn_small_applies(N, P1, P2, D, K)) {
-    launch_knn_small(a, norm);  // few queries: one wave per query (knn_small.hip)
-  } else {
-    const size_t need = knn_split_workspace_bytes(N, P1, P2, K);
-    launch_knn_bruteforce(a, norm, workspace != nullptr && workspace_bytes >= need && need > 0 ? workspace : nullptr);
+  const KnnPlan plan = knn_plan(N, P1, P2, D, K, version);
+  if (!workspace_fits(workspace, workspace_bytes, plan.workspace_bytes)) {
+    set_error("knn_points_idx: workspace of %zu bytes required (got %zu)", plan.workspace_bytes, workspace_bytes);
+    return POINTOPS_EWORKSPACE;
   }
+  int rc = POINTOPS_OK;
+  switch (plan.family) {
+    case KnnFamily::kGrid: rc = knn_grid_run(a, norm, workspace, reuse); break;
+    case KnnFamily::kWide: rc = launch_knn_wide(a, norm, plan.splits, workspace); break;
+    case KnnFamily::kGeneric: {
+      const dim3 grid((unsigned)(N * a.tiles));
+      if (norm == 1)
+        hipLaunchKernelGGL(knn_generic_kernel<1>, grid, dim3(kKnnBlock), 0, a.stream, p1, p2, lengths1,
+                           lengths2, a.P1, a.P2, a.D, a.K, a.tiles, idxs, dists);
+      else
+        hipLaunchKernelGGL(knn_generic_kernel<2>, grid, dim3(kKnnBlock), 0, a.stream, p1, p2, lengths1,
+                           lengths2, a.P1, a.P2, a.D, a.K, a.tiles, idxs, dists);
+      break;
+    }
+    case KnnFamily::kSmall: launch_knn_small(a, norm); break;
+    default: launch_knn_bruteforce(a, norm, plan.splits, workspace); break;  // kScan
+  }
+  if (rc != POINTOPS_OK) return rc;
   return check_launch("knn_points_idx");
 }
 

@@ -17,14 +17,21 @@ struct KnnArgs {
   hipStream_t stream;
 };
 
-// brute-force register-top-K scan (knn.hip); honours a.qlist / a.qcount.  With `workspace` (of
-// knn_split_workspace_bytes) a small batch is scanned in p2 slices and merged (knn_split_count > 1).
-void launch_knn_bruteforce(const KnnArgs& a, int norm, void* workspace = nullptr);
+// The kernel family of one knn_points_idx call (knn.hip), decided once: pointops_knn_workspace_bytes,
+// pointops_knn_uses_grid and the entry all read it.  kNone: nothing to search (N, P1 = 0 or D, K < 1).
+enum class KnnFamily { kNone, kGrid, kWide, kGeneric, kSmall, kScan };
+struct KnnPlan {
+  KnnFamily family;
+  int splits;              // p2 slices of the wide / scan families (1 = none), merged from partial lists
+  size_t workspace_bytes;  // the grid's, or the slices' partial lists
+};
+KnnPlan knn_plan(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K, int version);
 
-// p2 slices per query so that a small batch still fills the chip (1024 SIMDs): S partial lists per
-// query (64-bit (dist, idx) keys) are merged by knn_merge_partials
-int knn_split_count(int64_t N, int64_t P1, int64_t P2, int64_t K);
-size_t knn_split_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t K);
+// brute-force register-top-K scan (knn.hip); honours a.qlist / a.qcount.  With splits > 1 (the plan's, and a
+// `workspace` of its bytes) a small batch is scanned in p2 slices and merged.
+void launch_knn_bruteforce(const KnnArgs& a, int norm, int splits = 1, void* workspace = nullptr);
+
+// merges the S partial lists per query (64-bit (dist, idx) keys) of a scan in p2 slices
 void knn_merge_partials(const KnnArgs& a, int S, const void* workspace);
 
 // few queries (knn_small.hip): one wave per query, the cloud dealt over the lanes; D <= 8, K <= 32, no workspace
@@ -33,7 +40,7 @@ void launch_knn_small(const KnnArgs& a, int norm);
 
 // brute-force scan for any D / long lists (knn_wide.hip): LDS-transposed queries, register or LDS lists
 bool knn_wide_supported(int64_t D, int64_t K);
-int launch_knn_wide(const KnnArgs& a, int norm, void* workspace);
+int launch_knn_wide(const KnnArgs& a, int norm, int splits, void* workspace);
 
 // long lists, 64 < K <= 128: wave-per-query search of the 3x3x3 cube with one 2048-key sort (knn_grid_wsort.hip);
 // uncertified queries are appended to ws.fb2_list

@@ -92,7 +92,7 @@ static int knn_grid_run_slice(const KnnArgs& a, int norm, void* workspace, int r
     KnnArgs fa = a;
     fa.qlist = ws.fb2_list;
     fa.qcount = ws.fb2_count;
-    if ((rc = launch_knn_wide(fa, norm, nullptr)) != POINTOPS_OK) return rc;
+    if ((rc = launch_knn_wide(fa, norm, 1, nullptr)) != POINTOPS_OK) return rc;
     return check_launch("knn_points_idx(grid fallback)");
   }
   const int kc = grid_kc(a.K);
@@ -111,7 +111,7 @@ static int knn_grid_run_slice(const KnnArgs& a, int norm, void* workspace, int r
   fa.qlist = ws.fb2_list;
   fa.qcount = ws.fb2_count;
   if (a.K <= 32) launch_knn_bruteforce(fa, norm);
-  else if ((rc = launch_knn_wide(fa, norm, nullptr)) != POINTOPS_OK) return rc;  // 64-key lists (knn_wide.hip)
+  else if ((rc = launch_knn_wide(fa, norm, 1, nullptr)) != POINTOPS_OK) return rc;  // 64-key lists (knn_wide.hip)
   return check_launch("knn_points_idx(grid fallback)");
 }
 

@@ -277,11 +277,11 @@ bool knn_wide_supported(int64_t D, int64_t K) {
   return ((size_t)D * 4 + (size_t)K * 8) * 64 <= kWideLdsMax - 1024;
 }
 
-int launch_knn_wide(const KnnArgs& a, int norm, void* workspace) {
+int launch_knn_wide(const KnnArgs& a, int norm, int splits, void* workspace) {
   const int K = a.K;
   if (K <= 32) {
     // 64-lane workgroups while the batch is small (4x the workgroups), 256 lanes otherwise
-    const int S = knn_split_count(a.N, a.P1, a.P2, a.K);
+    const int S = splits;
     const bool small = a.N * ceil_div(a.P1, 256) < 2048;
     const size_t lds = (size_t)a.D * (small ? 64 : 256) * 4;
 #define PO_WIDE(KC)                                                                                                 \

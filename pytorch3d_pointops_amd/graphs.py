@@ -11,9 +11,10 @@ it with one `hipGraphLaunch`.
 Every operator of the package can be captured because the C ABI never synchronises, never allocates and takes every
 data-dependent decision (grid or scan per cloud, which fallback pass a query needs) ON THE DEVICE; the chamfer's
 reverse search forks to its side stream and joins back through events, which a capture follows.  The host side keeps
-three promises while `torch.cuda.is_current_stream_capturing()`: workspaces come from the graph's private pool
-(`_C._scratch`), the opt-in grid reuse is bypassed (a captured reuse level would be replayed blindly), and the lengths
-validation's device-to-host read has happened during the warm-up calls (`_common.lengths_max` remembers it).
+two promises while `torch.cuda.is_current_stream_capturing()`: the opt-in grid reuse is bypassed (a captured reuse
+level would be replayed blindly), and the lengths validation's device-to-host read has happened during the warm-up
+calls (`_common.lengths_max` remembers it).  Workspaces are allocated per call, so under capture they come from the
+graph's private pool like every other tensor of the captured calls.
 
     step = capture(lambda x, y: chamfer_distance(x, y)[0], (x, y), backward=True)
     loss, (gx, gy) = step(new_x, new_y)      # copies into the static inputs, replays, returns the static results
@@ -67,9 +68,8 @@ class GraphedCall:
             with torch.cuda.graph(self.graph):
                 self.outputs, self._single, self.grads = run()
         # tensors the captured launches may point at although no Python object of the capture owns them
-        from . import _C
         from .functions import _common
-        self._keepalive = (list(_common._LENGTHS_CACHE.values()), list(_C._SCRATCH.values()))
+        self._keepalive = list(_common._LENGTHS_CACHE.values())
 
     def replay(self) -> None:
         self.graph.replay()

@@ -95,6 +95,15 @@ def test_fps_validation_errors():
         sample_farthest_points(p, K=[1, 2, 3])
 
 
+def test_backward_det_workspace_covers_an_empty_target_cloud():
+    """The deterministic backward's workspace size is the layout its entries carve, for every shape they accept: with
+    no target points (M = 0) the table of N L K entries still needs its four key / value arrays."""
+    from pytorch3d_pointops_amd import _C
+
+    assert _C._lib.pointops_backward_det_workspace_bytes(1, 1024, 8, 0) >= 4 * 4 * 8192
+    assert _C._lib.pointops_backward_det_workspace_bytes(1, 1024, 8, 1) >= 4 * 4 * 8192
+
+
 def test_packed_validation_errors():
     from pytorch3d_pointops_amd.functions.packed_to_padded import _RaggedCopyFn, packed_to_padded, padded_to_packed
 

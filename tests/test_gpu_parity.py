@@ -1694,6 +1694,106 @@ def test_grid_reuse_between_calls(dev, oracle):
         po.set_grid_cache(False)
 
 
+def test_grid_cache_drops_the_entry_of_a_failed_call(dev, monkeypatch):
+    """A grid call whose native call fails leaves nothing in the grid cache: the next call of the same tensors builds
+    its grid again (a "miss") instead of reusing a workspace that may be half built."""
+    import pytorch3d_pointops_amd as po
+    from pytorch3d_pointops_amd import _C
+
+    ta, tb = G(cases.cloud(3511, (2, 9000, 3)), dev), G(cases.cloud(3512, (2, 12000, 3)), dev)
+    tl1, tl2 = G(np.array([9000, 9000]), dev), G(np.array([12000, 11000]), dev)
+    assert _C._lib.pointops_knn_uses_grid(2, 9000, 12000, 3, 16, 3)
+    check = _C._check
+    failed = []
+
+    def fail_once(code, what):
+        if not failed:
+            failed.append(what)
+            raise RuntimeError("injected failure")
+        return check(code, what)
+
+    try:
+        po.set_grid_cache(True)
+        monkeypatch.setattr(_C, "_check", fail_once)
+        with pytest.raises(RuntimeError, match="injected failure"):
+            _C.knn_points_idx(ta, tb, tl1, tl2, 2, 16, 3)
+        assert not any(v["p2"]() is tb for v in _C._GRID_CACHE.values())
+        before = dict(_C.grid_cache_stats)
+        i, d = _C.knn_points_idx(ta, tb, tl1, tl2, 2, 16, 3)
+        assert _C.grid_cache_stats["miss"] == before["miss"] + 1
+        po.set_grid_cache(False)
+        fi, fd = _C.knn_points_idx(ta, tb, tl1, tl2, 2, 16, 3)
+        assert torch.equal(i, fi) and torch.equal(d, fd)
+    finally:
+        po.set_grid_cache(False)
+
+
+def test_workspaces_are_private_to_each_call_across_host_threads(dev):
+    """Two host threads enqueue on the same stream at once (ctypes releases the GIL in every native call): a
+    grid-searched knn_points (2 MB of workspace) and the one-call chamfer, 50 times each.  Every call has a workspace of
+    its own, so every result is bit-equal to the single-threaded one."""
+    import threading
+
+    from pytorch3d_pointops_amd.functions import knn_points
+    from pytorch3d_pointops_amd.functions.chamfer import chamfer_distance
+
+    p1, p2 = G(cases.cloud(3521, (4, 4096, 3)), dev), G(cases.cloud(3522, (4, 4096, 3)), dev)
+    x, y = G(cases.cloud(3523, (4, 2048, 3)), dev), G(cases.cloud(3524, (4, 2048, 3)), dev)
+    jobs = {"knn": lambda: knn_points(p1, p2, K=24, return_sorted=True)[:2],
+            "chamfer": lambda: (chamfer_distance(x, y)[0],)}
+    want = {k: fn() for k, fn in jobs.items()}
+    got, errors = {}, []
+
+    def run(name):
+        try:
+            torch.cuda.set_device(dev)
+            got[name] = [jobs[name]() for _ in range(50)]
+        except BaseException as e:  # reported by the main thread
+            errors.append(e)
+
+    threads = [threading.Thread(target=run, args=(k,)) for k in jobs]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    torch.cuda.synchronize()
+    assert not errors, errors
+    for k, runs in got.items():
+        assert len(runs) == 50
+        for r in runs:
+            assert all(torch.equal(a, b) for a, b in zip(r, want[k])), k
+
+
+def test_chamfer_of_an_empty_batch_is_zero(dev):
+    """The one-call chamfer of N = 0 clouds writes its batch-reduced outputs: exactly 0, as the composed path's batch
+    reduction gives (a freed NaN block of the output's size shows uninitialised memory)."""
+    from pytorch3d_pointops_amd.functions.chamfer import chamfer_distance
+
+    x, y = torch.zeros((0, 64, 3), device=dev), torch.zeros((0, 80, 3), device=dev)
+    for red in ("mean", "sum"):
+        junk = torch.full((), float("nan"), device=dev)
+        del junk
+        loss, feats = chamfer_distance(x, y, batch_reduction=red)
+        assert loss.shape == () and feats is None
+        assert loss.item() == 0.0, red
+
+
+def test_deterministic_knn_backward_with_an_empty_target(dev):
+    """The deterministic knn_points backward with no target points (P2 = 0) stays inside its workspace and matches
+    the default backward: every query's neighbours are padding, so both gradients are zero."""
+    from pytorch3d_pointops_amd import _C
+
+    p1 = G(cases.cloud(3531, (2, 1024, 3)), dev)
+    p2 = torch.zeros((2, 0, 3), device=dev)
+    l1, l2 = G(np.array([1024, 700]), dev), G(np.array([0, 0]), dev)
+    idx = torch.zeros((2, 1024, 8), dtype=torch.int64, device=dev)  # what the forward writes for empty targets
+    grad = torch.rand(idx.shape, generator=torch.Generator().manual_seed(3532)).to(dev)
+    for norm in (1, 2):
+        d1, d2 = _C.knn_points_backward(p1, p2, l1, l2, idx, norm, grad, deterministic=True)
+        a1, a2 = _C.knn_points_backward(p1, p2, l1, l2, idx, norm, grad)
+        assert torch.equal(d1, a1) and d2.shape == a2.shape == (2, 0, 3)
+
+
 def _bruteforce_rows(q, pts, K):
     """(idx, dists) of the K nearest of `pts` for every row of `q` by a dense torch distance table with the kernels'
     expression ((dx*dx + dy*dy) + dz*dz) and lexicographic (dist, idx) order (stable sort)."""
