@@ -209,21 +209,17 @@ extern "C" int pointops_knn_points_backward_det(const float* p1, const float* p2
   if (rc != POINTOPS_OK) return rc;
   if (N * P2 * D > 0) {
     const unsigned b2 = (unsigned)ceil_div(N * P2 * D, kDetBlock);
-    if (norm == 1)
-      hipLaunchKernelGGL(det_knn_p2_kernel<1>, dim3(b2), dim3(kDetBlock), 0, stream, p1, p2, grad_dists, ws.vals_out,
+    with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+      hipLaunchKernelGGL(det_knn_p2_kernel<NORM>, dim3(b2), dim3(kDetBlock), 0, stream, p1, p2, grad_dists, ws.vals_out,
                          ws.seg_start, ws.seg_end, N * P2, (int)P1, (int)P2, (int)D, (int)K, grad_p2);
-    else
-      hipLaunchKernelGGL(det_knn_p2_kernel<2>, dim3(b2), dim3(kDetBlock), 0, stream, p1, p2, grad_dists, ws.vals_out,
-                         ws.seg_start, ws.seg_end, N * P2, (int)P1, (int)P2, (int)D, (int)K, grad_p2);
+    });
   }
   if (N * P1 * D > 0) {
     const unsigned b1 = (unsigned)ceil_div(N * P1 * D, kDetBlock);
-    if (norm == 1)
-      hipLaunchKernelGGL(det_knn_p1_kernel<1>, dim3(b1), dim3(kDetBlock), 0, stream, p1, p2, lengths1, lengths2, idxs,
+    with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+      hipLaunchKernelGGL(det_knn_p1_kernel<NORM>, dim3(b1), dim3(kDetBlock), 0, stream, p1, p2, lengths1, lengths2, idxs,
                          grad_dists, N * P1, (int)P1, (int)P2, (int)D, (int)K, grad_p1);
-    else
-      hipLaunchKernelGGL(det_knn_p1_kernel<2>, dim3(b1), dim3(kDetBlock), 0, stream, p1, p2, lengths1, lengths2, idxs,
-                         grad_dists, N * P1, (int)P1, (int)P2, (int)D, (int)K, grad_p1);
+    });
   }
   return check_launch("knn_points_backward(deterministic)");
 }

@@ -329,20 +329,6 @@ size_t ball_grid_workspace_bytes(int64_t N, int64_t P1, int64_t P2) {
   return grid_carve(nullptr, nullptr, N, P1, P2, kBallCellTarget, true);
 }
 
-template <int D>
-static void ball_run_d(const KnnArgs& a, float radius2, const GridWs& ws, int wgs) {
-#define PO_BALL(KC)                                                                                              \
-  hipLaunchKernelGGL((ball_grid_lane_kernel<D, KC>), dim3((unsigned)wgs), dim3(kGridWave), 0, a.stream, a.p1, a.p2, \
-                     (const GridCloud*)ws.cloud, (const int*)ws.chunk_prefix, (const float*)ws.edges,            \
-                     (const int*)ws.cell_start, (const float4*)ws.sorted, (const float4*)ws.qsorted, ws.fb2_count,    \
-                     ws.fb2_list, ws.cell_cap, a.P1, a.P2, a.K, (int)a.N, radius2, a.idxs, a.dists)
-  if (a.K <= 8) PO_BALL(8);
-  else if (a.K <= 16) PO_BALL(16);
-  else if (a.K <= 32) PO_BALL(32);
-  else PO_BALL(64);
-#undef PO_BALL
-}
-
 // Builds the grids and answers every query it can certify.  On return (stream order) flag[n] = 1 for
 // the clouds that were searched through their grid -- for those only the qcount[n] queries of
 // qlist[n * P1 ..] are left -- and 0 for the clouds the index-order scan has to do in full.
@@ -367,25 +353,22 @@ int ball_grid_run(const KnnArgs& a, float radius, void* workspace, const int** f
   chunks = (chunks + 7) / 8 * 8;
   const int wgs = (int)(chunks < 2048 ? 2048 : (chunks > (1 << 20) ? (1 << 20) : chunks));
   const float radius2 = radius * radius;  // fp32 product (ball_query_cpu.cpp:26)
-  switch (a.D) {
-    case 1: ball_run_d<1>(a, radius2, ws, wgs); break;
-    case 2: ball_run_d<2>(a, radius2, ws, wgs); break;
-    default: ball_run_d<3>(a, radius2, ws, wgs); break;
-  }
+  with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) {
+    with_bucket(Ints<8, 16, 32, 64>{}, a.K, [&](auto KC) {
+      hipLaunchKernelGGL((ball_grid_lane_kernel<D, KC>), dim3((unsigned)wgs), dim3(kGridWave), 0, a.stream, a.p1, a.p2,
+                         (const GridCloud*)ws.cloud, (const int*)ws.chunk_prefix, (const float*)ws.edges,
+                         (const int*)ws.cell_start, (const float4*)ws.sorted, (const float4*)ws.qsorted, ws.fb2_count,
+                         ws.fb2_list, ws.cell_cap, a.P1, a.P2, a.K, (int)a.N, radius2, a.idxs, a.dists);
+    });
+  });
   // scan-mode clouds: all queries, ordered by coarse cell
   if (debug_knob("ball_order", 1) != 0) {
     const dim3 og((unsigned)ceil_div(a.P1, kOrderBlock * kOrderPerThread), (unsigned)a.N);
-#define PO_ORDER(DD)                                                                                         \
-  hipLaunchKernelGGL((ball_order_kernel<DD, false>), og, dim3(kOrderBlock), 0, a.stream, a.p1, a.P1, ws);     \
-  hipLaunchKernelGGL(ball_order_scan_kernel, dim3((unsigned)a.N), dim3(kOrderScanBlock), 0, a.stream, ws,    \
-                     (int)og.x);                                                                             \
-  hipLaunchKernelGGL((ball_order_kernel<DD, true>), og, dim3(kOrderBlock), 0, a.stream, a.p1, a.P1, ws)
-    switch (a.D) {
-      case 1: PO_ORDER(1); break;
-      case 2: PO_ORDER(2); break;
-      default: PO_ORDER(3); break;
-    }
-#undef PO_ORDER
+    with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) {
+      hipLaunchKernelGGL((ball_order_kernel<D, false>), og, dim3(kOrderBlock), 0, a.stream, a.p1, a.P1, ws);
+      hipLaunchKernelGGL(ball_order_scan_kernel, dim3((unsigned)a.N), dim3(kOrderScanBlock), 0, a.stream, ws, (int)og.x);
+      hipLaunchKernelGGL((ball_order_kernel<D, true>), og, dim3(kOrderBlock), 0, a.stream, a.p1, a.P1, ws);
+    });
   }
   *flag = ws.grid_flag;
   *qcount = ws.fb2_count;

@@ -491,30 +491,16 @@ extern "C" int pointops_ball_query(const float* p1, const float* p2, const int64
   if (staged) {
     const size_t lds = (size_t)kBqListWaves * kWave * ball_stage_stride((int)K) * sizeof(unsigned);
     const dim3 lgrid((unsigned)ceil_div(P1, kWave * kBqListWaves), (unsigned)N);
-#define PO_LIST(DT)                                                                                               \
-  hipLaunchKernelGGL((ball_query_list_kernel<DT>), lgrid, dim3(kWave * kBqListWaves), lds, stream, p1, p2,       \
-                     lengths1, lengths2,                                                                          \
-                     (int)P1, (int)P2, (int)K, radius2, flag, qcount, qlist, idxs, dists)
-    switch (D) {
-      case 1: PO_LIST(1); break;
-      case 2: PO_LIST(2); break;
-      case 3: PO_LIST(3); break;
-      default: PO_LIST(4); break;
-    }
-#undef PO_LIST
+    with_exact<4>(Ints<1, 2, 3>{}, (int)D, [&](auto DT) {
+      hipLaunchKernelGGL((ball_query_list_kernel<DT>), lgrid, dim3(kWave * kBqListWaves), lds, stream, p1, p2, lengths1,
+                         lengths2, (int)P1, (int)P2, (int)K, radius2, flag, qcount, qlist, idxs, dists);
+    });
     return check_launch("ball_query(list)");
   }
   const dim3 grid((unsigned)(N * tiles)), block(kBqBlock);
-#define PO_LAUNCH(DT)                                                                            \
-  hipLaunchKernelGGL((ball_query_kernel<DT>), grid, block, 0, stream, p1, p2, lengths1, lengths2, \
-                     (int)P1, (int)P2, (int)D, (int)K, radius2, tiles, flag, qcount, qlist, idxs, dists)
-  switch (D) {
-    case 1: PO_LAUNCH(1); break;
-    case 2: PO_LAUNCH(2); break;
-    case 3: PO_LAUNCH(3); break;
-    case 4: PO_LAUNCH(4); break;
-    default: PO_LAUNCH(0); break;
-  }
-#undef PO_LAUNCH
+  with_exact<0>(Ints<1, 2, 3, 4>{}, (int)D, [&](auto DT) {
+    hipLaunchKernelGGL((ball_query_kernel<DT>), grid, block, 0, stream, p1, p2, lengths1, lengths2, (int)P1, (int)P2,
+                       (int)D, (int)K, radius2, tiles, flag, qcount, qlist, idxs, dists);
+  });
   return check_launch("ball_query");
 }

@@ -121,17 +121,10 @@ void launch_ball_small(const float* p1, const float* p2, const int64_t* lengths1
   const int qw = (int)std::min<int64_t>(std::max<int64_t>(ceil_div(tq, (int64_t)16384), 1), 64);
   const int64_t wpc = ceil_div(P1, (int64_t)qw), total = N * wpc;
   const dim3 grid((unsigned)ceil_div(total, (int64_t)kBsWaves));
-#define PO_BS(DT)                                                                                              \
-  hipLaunchKernelGGL((ball_small_kernel<DT>), grid, dim3(kBsWaves * 64), 0, stream, p1, p2, lengths1, lengths2, \
-                     (int)P1, (int)P2, (int)D, (int)K, radius2, qw, (int)wpc, (int)total, idxs, dists)
-  switch (D) {
-    case 1: PO_BS(1); break;
-    case 2: PO_BS(2); break;
-    case 3: PO_BS(3); break;
-    case 4: PO_BS(4); break;
-    default: PO_BS(0); break;
-  }
-#undef PO_BS
+  with_exact<0>(Ints<1, 2, 3, 4>{}, (int)D, [&](auto DT) {
+    hipLaunchKernelGGL((ball_small_kernel<DT>), grid, dim3(kBsWaves * 64), 0, stream, p1, p2, lengths1, lengths2, (int)P1,
+                       (int)P2, (int)D, (int)K, radius2, qw, (int)wpc, (int)total, idxs, dists);
+  });
 }
 
 }  // namespace pointops

@@ -419,21 +419,17 @@ static int chamfer_backward_impl(const float* x, const float* y, const int64_t* 
   for (int f = 0; f < F; ++f) four = four && C[f] <= 4;
   if (four) {
     const dim3 grid4((unsigned)ceil_div(P1 * 4, kCfBlock), (unsigned)N), block4(kCfBlock);
-    if (norm == 1)
-      hipLaunchKernelGGL(chamfer_backward4_kernel<1>, grid4, block4, 0, stream, x, y, idx, x_lengths, y_lengths,
+    with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+      hipLaunchKernelGGL(chamfer_backward4_kernel<NORM>, grid4, block4, 0, stream, x, y, idx, x_lengths, y_lengths,
                          weights, grad_out, (int)N, P1, P2, (int)D, ft, abs_cosine, mean, acc, grad_x, grad_y);
-    else
-      hipLaunchKernelGGL(chamfer_backward4_kernel<2>, grid4, block4, 0, stream, x, y, idx, x_lengths, y_lengths,
-                         weights, grad_out, (int)N, P1, P2, (int)D, ft, abs_cosine, mean, acc, grad_x, grad_y);
+    });
     return check_launch("chamfer_backward");
   }
   const dim3 grid((unsigned)ceil_div(P1, kCfBlock), (unsigned)N), block(kCfBlock);
-  if (norm == 1)
-    hipLaunchKernelGGL(chamfer_backward_kernel<1>, grid, block, 0, stream, x, y, idx, x_lengths, y_lengths, weights,
+  with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+    hipLaunchKernelGGL(chamfer_backward_kernel<NORM>, grid, block, 0, stream, x, y, idx, x_lengths, y_lengths, weights,
                        grad_out, (int)N, P1, P2, (int)D, ft, abs_cosine, mean, acc, grad_x, grad_y);
-  else
-    hipLaunchKernelGGL(chamfer_backward_kernel<2>, grid, block, 0, stream, x, y, idx, x_lengths, y_lengths, weights,
-                       grad_out, (int)N, P1, P2, (int)D, ft, abs_cosine, mean, acc, grad_x, grad_y);
+  });
   return check_launch("chamfer_backward");
 }
 

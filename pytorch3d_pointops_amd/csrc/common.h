@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/pointops_amd.h"
+#include "dispatch.h"
 
 // Parity rule: every distance is an UNFUSED fp32
 // multiply followed by an add.  hipcc's default -ffp-contract=fast would fuse

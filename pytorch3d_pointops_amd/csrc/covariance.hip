@@ -218,15 +218,16 @@ extern "C" int pointops_point_covariances(const float* knn, int64_t N, int64_t P
   if (K * D <= kCovStageMax) {
     const dim3 gs((unsigned)ceil_div(rows, kCovTile)), bs(kCovTile);
     const size_t lds = sizeof(float) * (size_t)kCovTile * (size_t)(K * D + 1);
-    if (D == 3) hipLaunchKernelGGL((covariance_staged_kernel<3, false>), gs, bs, lds, stream, knn, nullptr, rows, (int)K, 3, cov);
-    else if (D == 2) hipLaunchKernelGGL((covariance_staged_kernel<2, false>), gs, bs, lds, stream, knn, nullptr, rows, (int)K, 2, cov);
-    else hipLaunchKernelGGL((covariance_staged_kernel<0, false>), gs, bs, lds, stream, knn, nullptr, rows, (int)K, (int)D, cov);
+    with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
+      hipLaunchKernelGGL((covariance_staged_kernel<DT, false>), gs, bs, lds, stream, knn, nullptr, rows, (int)K, (int)D,
+                         cov);
+    });
     return check_launch("point_covariances");
   }
   const dim3 grid((unsigned)blocks), block(kCovBlock);
-  if (D == 3) hipLaunchKernelGGL(covariance_kernel<3>, grid, block, 0, stream, knn, rows, (int)K, 3, cov);
-  else if (D == 2) hipLaunchKernelGGL(covariance_kernel<2>, grid, block, 0, stream, knn, rows, (int)K, 2, cov);
-  else hipLaunchKernelGGL(covariance_kernel<0>, grid, block, 0, stream, knn, rows, (int)K, (int)D, cov);
+  with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
+    hipLaunchKernelGGL(covariance_kernel<DT>, grid, block, 0, stream, knn, rows, (int)K, (int)D, cov);
+  });
   return check_launch("point_covariances");
 }
 
@@ -242,18 +243,16 @@ extern "C" int pointops_point_covariances_backward(const float* knn, const float
   if (K * D <= kCovStageMax) {
     const dim3 gs((unsigned)ceil_div(rows, kCovTile)), bs(kCovTile);
     const size_t lds = sizeof(float) * (size_t)kCovTile * (size_t)(K * D + 1);
-    if (D == 3) hipLaunchKernelGGL((covariance_staged_kernel<3, true>), gs, bs, lds, stream, knn, grad_cov, rows, (int)K, 3, grad_knn);
-    else if (D == 2) hipLaunchKernelGGL((covariance_staged_kernel<2, true>), gs, bs, lds, stream, knn, grad_cov, rows, (int)K, 2, grad_knn);
-    else hipLaunchKernelGGL((covariance_staged_kernel<0, true>), gs, bs, lds, stream, knn, grad_cov, rows, (int)K, (int)D, grad_knn);
+    with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
+      hipLaunchKernelGGL((covariance_staged_kernel<DT, true>), gs, bs, lds, stream, knn, grad_cov, rows, (int)K, (int)D,
+                         grad_knn);
+    });
     return check_launch("point_covariances_backward");
   }
   const dim3 grid((unsigned)blocks), block(kCovBlock);
-  if (D == 3)
-    hipLaunchKernelGGL(covariance_backward_kernel<3>, grid, block, 0, stream, knn, grad_cov, rows, (int)K, 3, grad_knn);
-  else if (D == 2)
-    hipLaunchKernelGGL(covariance_backward_kernel<2>, grid, block, 0, stream, knn, grad_cov, rows, (int)K, 2, grad_knn);
-  else
-    hipLaunchKernelGGL(covariance_backward_kernel<0>, grid, block, 0, stream, knn, grad_cov, rows, (int)K, (int)D,
+  with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
+    hipLaunchKernelGGL(covariance_backward_kernel<DT>, grid, block, 0, stream, knn, grad_cov, rows, (int)K, (int)D,
                        grad_knn);
+  });
   return check_launch("point_covariances_backward");
 }

@@ -596,6 +596,15 @@ static int fps_resident_blocks(Kernel kernel) {
   return fps_num_cus() * (per_cu > 1 ? 1 : per_cu);  // one 1024-lane workgroup per CU is what the plan uses
 }
 
+// the (D, points per lane) instances of the small and the cluster kernels: D in {2, 3}, the smallest PPT >= ppt
+constexpr Ints<4, 8, 16> kFpsPpt{};
+template <class F>
+static auto with_fps_instance(int D, int ppt, F&& f) {
+  return with_exact<2>(Ints<3, 2>{}, D, [&](auto DT) {
+    return with_bucket(kFpsPpt, ppt, [&](auto PPT) { return f(DT, PPT); });
+  });
+}
+
 // workgroups per cloud of the plan for the worst D (the size query has no D): only D = 3 may take fewer points per lane
 static int fps_max_groups(int64_t N, int64_t P) {
   int ppt, G;
@@ -644,41 +653,27 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
   fps_carve(&ws, workspace, N, P, max_K, G);
   hipStream_t stream = (hipStream_t)stream_;
 
-#define PO_LAUNCH(DT, FLAGS)                                                                      \
-  hipLaunchKernelGGL((fps_kernel<DT>), dim3((unsigned)N), dim3(kFpsBlock), 0, stream, points, lengths, K, \
-                     start_idxs, (int)P, (int)D, (int)max_K, idxs, ws.min_dist, FLAGS)
+  // v1: one workgroup per cloud (flags: only the clouds flagged there)
+  auto launch_v1 = [&](auto DT, const unsigned* flags) {
+    hipLaunchKernelGGL((fps_kernel<DT>), dim3((unsigned)N), dim3(kFpsBlock), 0, stream, points, lengths, K, start_idxs,
+                       (int)P, (int)D, (int)max_K, idxs, ws.min_dist, flags);
+  };
   // small clouds: one four-wave workgroup per cloud
   if ((D == 3 || D == 2) && P >= 1 && P <= 16 * kFpsSmallBlock && debug_knob("fps_small", 1) != 0) {
-#define PO_SMALL(DT, PPT)                                                                                          \
-  hipLaunchKernelGGL((fps_small_kernel<DT, PPT>), dim3((unsigned)N), dim3(kFpsSmallBlock), 0, stream, points, lengths, K, \
-                     start_idxs, (int)P, (int)max_K, idxs)
-    if (D == 3) {
-      if (P <= 4 * kFpsSmallBlock) PO_SMALL(3, 4);
-      else if (P <= 8 * kFpsSmallBlock) PO_SMALL(3, 8);
-      else PO_SMALL(3, 16);
-    } else {
-      if (P <= 4 * kFpsSmallBlock) PO_SMALL(2, 4);
-      else if (P <= 8 * kFpsSmallBlock) PO_SMALL(2, 8);
-      else PO_SMALL(2, 16);
-    }
-#undef PO_SMALL
+    with_fps_instance((int)D, (int)ceil_div(P, kFpsSmallBlock), [&](auto DT, auto PPT) {
+      hipLaunchKernelGGL((fps_small_kernel<DT, PPT>), dim3((unsigned)N), dim3(kFpsSmallBlock), 0, stream, points,
+                         lengths, K, start_idxs, (int)P, (int)max_K, idxs);
+    });
     return check_launch("sample_farthest_points(small)");
   }
   // v2 (register-resident clusters) for D in {2,3}: up to PPT*1024 points per workgroup
   if ((D == 3 || D == 2) && P >= 1) {
-    int resident = 0;
-#define PO_RES(DT, PPT) resident = fps_resident_blocks(fps_cluster_kernel<DT, PPT>)
-    if (D == 3) {
-      if (ppt == 4) PO_RES(3, 4);
-      else if (ppt == 8) PO_RES(3, 8);
-      else PO_RES(3, 16);
-    } else {
-      if (ppt == 4) PO_RES(2, 4);
-      else if (ppt == 8) PO_RES(2, 8);
-      else PO_RES(2, 16);
-    }
-#undef PO_RES
-    if (G <= resident) {
+    bool cluster = false;
+    const int v2 = with_fps_instance((int)D, ppt, [&](auto DT, auto PPT) {
+      // the residency of the instance that is launched: the exchange needs every workgroup of a cluster resident
+      const int resident = fps_resident_blocks(fps_cluster_kernel<DT, PPT>);
+      if (G > resident) return POINTOPS_OK;
+      cluster = true;
       int mode = (int)debug_knob("fps_mode", 2);
       const int per_xcd = resident / kXcds;  // blocks that share an XCD under round-robin dispatch
       if (G > per_xcd || per_xcd < 1) mode = 0;  // a cloud does not fit one XCD: spread it (agent-scope exchange)
@@ -697,34 +692,19 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
       // XCD-local numbering: cluster c = (j / G) * 8 + x for the j-th block of XCD group x
       const int blocks = mode == 0 ? n_clusters * G : (int)ceil_div(n_clusters, kXcds) * G * kXcds;
       const unsigned spin_limit = (unsigned)debug_knob("fps_spin_limit", 1 << 20);
-      const dim3 grid((unsigned)blocks), block(kFpsBlock);
-#define PO_LAUNCH_C(DT, PPT)                                                                         \
-  hipLaunchKernelGGL((fps_cluster_kernel<DT, PPT>), grid, block, 0, stream, points, lengths, K, start_idxs, \
-                     (int)N, (int)P, (int)max_K, G, n_clusters, mode, spin_limit, ws.slots, ws.timeout_flags, idxs)
-      if (D == 3) {
-        if (ppt == 4) PO_LAUNCH_C(3, 4);
-        else if (ppt == 8) PO_LAUNCH_C(3, 8);
-        else PO_LAUNCH_C(3, 16);
-      } else {
-        if (ppt == 4) PO_LAUNCH_C(2, 4);
-        else if (ppt == 8) PO_LAUNCH_C(2, 8);
-        else PO_LAUNCH_C(2, 16);
-      }
-#undef PO_LAUNCH_C
-      int rc = check_launch("sample_farthest_points");
-      if (rc != POINTOPS_OK || G == 1) return rc;
+      hipLaunchKernelGGL((fps_cluster_kernel<DT, PPT>), dim3((unsigned)blocks), dim3(kFpsBlock), 0, stream, points,
+                         lengths, K, start_idxs, (int)N, (int)P, (int)max_K, G, n_clusters, mode, spin_limit, ws.slots,
+                         ws.timeout_flags, idxs);
+      return check_launch("sample_farthest_points");
+    });
+    if (cluster) {
+      if (v2 != POINTOPS_OK || G == 1) return v2;
       // repair pass: clouds whose exchange timed out (CUs taken away by another kernel or a CU mask) are
       // redone by the single-workgroup kernel; a cloud that was not flagged returns at once
-      if (D == 3) PO_LAUNCH(3, (const unsigned*)ws.timeout_flags);
-      else PO_LAUNCH(2, (const unsigned*)ws.timeout_flags);
+      with_exact<2>(Ints<3, 2>{}, (int)D, [&](auto DT) { launch_v1(DT, (const unsigned*)ws.timeout_flags); });
       return check_launch("sample_farthest_points(repair)");
     }
   }
-  switch (D) {
-    case 2: PO_LAUNCH(2, nullptr); break;
-    case 3: PO_LAUNCH(3, nullptr); break;
-    default: PO_LAUNCH(0, nullptr); break;
-  }
-#undef PO_LAUNCH
+  with_exact<0>(Ints<2, 3>{}, (int)D, [&](auto DT) { launch_v1(DT, nullptr); });
   return check_launch("sample_farthest_points");
 }

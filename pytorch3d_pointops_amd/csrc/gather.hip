@@ -135,13 +135,9 @@ extern "C" int pointops_gather_neighbors(const float* x, const int64_t* idx, con
     hipStream_t stream = (hipStream_t)stream_;
     if (U <= 4) {
       const dim3 grid((unsigned)ceil_div(LK, kGaBlock), (unsigned)N), block(kGaBlock);
-#define PO_ROWS(UU) \
-  hipLaunchKernelGGL(gather_rows_kernel<UU>, grid, block, 0, stream, x, idx, lengths, (int)M, (int)LK, (int)K, out)
-      if (U == 1) PO_ROWS(1);
-      else if (U == 2) PO_ROWS(2);
-      else if (U == 3) PO_ROWS(3);
-      else PO_ROWS(4);
-#undef PO_ROWS
+      with_exact<4>(Ints<1, 2, 3>{}, (int)U, [&](auto UU) {
+        hipLaunchKernelGGL(gather_rows_kernel<UU>, grid, block, 0, stream, x, idx, lengths, (int)M, (int)LK, (int)K, out);
+      });
     } else {
       const dim3 grid((unsigned)ceil_div(LK * U, kGaBlock), (unsigned)N), block(kGaBlock);
       hipLaunchKernelGGL(gather_elems32_kernel, grid, block, 0, stream, x, idx, lengths, (int)M, (int)U, (int)LK,
@@ -172,17 +168,11 @@ extern "C" int pointops_gather_neighbors_backward(const float* grad_out, const i
   if (total == 0) return POINTOPS_OK;
   if (plan.tiled) {
     const DivMagic dm = division_magic((unsigned)K);
-#define PO_TILED(C)                                                                                          \
-  do {                                                                                                       \
-    const GatherGradSrc<C> src{grad_out, lengths, (int)L, (int)K};                                           \
-    hipLaunchKernelGGL((tiled_scatter_kernel<GatherGradSrc<C>>), plan.grid, dim3(kTiledBlock), 0, stream,    \
-                       src, idx, (int)N, (int)L, (int)M, (int)K, dm, plan.parts, plan.S, grad_x);            \
-  } while (0)
-    if (U == 1) PO_TILED(1);
-    else if (U == 2) PO_TILED(2);
-    else if (U == 3) PO_TILED(3);
-    else PO_TILED(4);
-#undef PO_TILED
+    with_exact<4>(Ints<1, 2, 3>{}, (int)U, [&](auto C) {
+      const GatherGradSrc<C> src{grad_out, lengths, (int)L, (int)K};
+      hipLaunchKernelGGL((tiled_scatter_kernel<GatherGradSrc<C>>), plan.grid, dim3(kTiledBlock), 0, stream, src, idx,
+                         (int)N, (int)L, (int)M, (int)K, dm, plan.parts, plan.S, grad_x);
+    });
     return check_launch("gather_neighbors_backward(tiled)");
   }
   const int64_t blocks = ceil_div(total, kGaBlock);

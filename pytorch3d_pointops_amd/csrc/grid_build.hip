@@ -883,19 +883,20 @@ static void build_d(const KnnArgs& a, const GridWs& ws, int sets_mode, int refin
   const unsigned sets = sets_mode == 2 ? 2u : 1u;
   const int zbase = sets_mode == 1 ? 1 : 0;
   const int64_t pmax = same ? a.P2 : sets_mode == 1 ? a.P1 : (a.P2 > a.P1 ? a.P2 : a.P1);
-#define PO_PART(SCT, QRY)                                                                                         \
-  hipLaunchKernelGGL((grid_partition_kernel<D, SCT, QRY>),                                                        \
-                     dim3((unsigned)ceil_div(pmax, kPartBlock * (SCT ? kScatterPerThread : kCountPerThread)),     \
-                          (unsigned)a.N, sets),                                                                   \
-                     dim3(kPartBlock), 0, a.stream, a.p2, a.P2, a.p1, a.P1, a.K, ws, zbase, a.idxs, a.dists)
+  // count, then scatter, the points (self-query) or both sets
+  auto part = [&](auto scatter, auto queries) {
+    hipLaunchKernelGGL((grid_partition_kernel<D, scatter, queries>),
+                       dim3((unsigned)ceil_div(pmax, kPartBlock * (scatter ? kScatterPerThread : kCountPerThread)),
+                            (unsigned)a.N, sets),
+                       dim3(kPartBlock), 0, a.stream, a.p2, a.P2, a.p1, a.P1, a.K, ws, zbase, a.idxs, a.dists);
+  };
   if (same) {
-    PO_PART(false, false);
-    PO_PART(true, false);
+    part(std::false_type{}, std::false_type{});
+    part(std::true_type{}, std::false_type{});
   } else {
-    PO_PART(false, true);
-    PO_PART(true, true);
+    part(std::false_type{}, std::true_type{});
+    part(std::true_type{}, std::true_type{});
   }
-#undef PO_PART
   // sort workgroups per (cloud, set): enough of them to fill the chip when the batch is small
   // (a cloud of P entries has at most P / kCoarsePoints + cells / kFineMax + 2 bins)
   const int64_t bins = pmax / kCoarsePoints + ws.cell_cap / kFineMax + 2;
@@ -967,11 +968,7 @@ int grid_build_queries(const KnnArgs& a, const GridWs& ws, bool same, int level)
     hipLaunchKernelGGL(grid_pad_prefix_kernel, dim3((unsigned)ceil_div(a.P1, kPartBlock * kCountPerThread), (unsigned)a.N),
                        dim3(kPartBlock), 0, a.stream, ws, a.P1, a.K, a.idxs, a.dists);
   } else {
-    switch (a.D) {
-      case 1: build_d<1>(a, ws, 1, -1); break;
-      case 2: build_d<2>(a, ws, 1, -1); break;
-      default: build_d<3>(a, ws, 1, -1); break;
-    }
+    with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) { build_d<D>(a, ws, 1, -1); });
   }
   return check_launch("grid build (queries)");
 }
@@ -983,11 +980,7 @@ int grid_build(const KnnArgs& a, const GridWs& ws, const GridBuild& b) {
   hipLaunchKernelGGL(grid_setup_kernel, dim3((unsigned)a.N), dim3(kSetupBlock), 0, a.stream, a.p2, a.l1, a.l2, a.P1,
                      a.P2, a.D, b.c_target, b.h_min, b.ball_radius, b.ball_K, b.ball_factor, b.same ? 1 : 0, bbox_slots,
                      ws);
-  switch (a.D) {
-    case 1: build_d<1>(a, ws, b.same ? 0 : 2, b.refine); break;
-    case 2: build_d<2>(a, ws, b.same ? 0 : 2, b.refine); break;
-    default: build_d<3>(a, ws, b.same ? 0 : 2, b.refine); break;
-  }
+  with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) { build_d<D>(a, ws, b.same ? 0 : 2, b.refine); });
   return check_launch("grid build");
 }
 

@@ -153,23 +153,18 @@ int grid_refine(const KnnArgs& a, const GridWs& ws) {
   // (a workgroup claims 128 KB of LDS = one CU: up to 256 of them chip-wide, at least kRefineWgs per cloud)
   const int64_t per_cloud = 256 / (a.N > 0 ? a.N : 1);
   const dim3 grid((unsigned)(per_cloud < kRefineWgs ? kRefineWgs : (per_cloud > 64 ? 64 : per_cloud)), (unsigned)a.N);
-#define PO_REFINE(DD)                                                                                            \
-  {                                                                                                              \
-    static bool attr = false;                                                                                    \
-    if (!attr) {                                                                                                 \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(grid_refine_build_kernel<DD>),                       \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)               \
-        return check_launch("grid refine attribute");                                                            \
-      attr = true;                                                                                               \
-    }                                                                                                            \
-    hipLaunchKernelGGL((grid_refine_build_kernel<DD>), grid, dim3(kRefineBlock), lds, a.stream, ws, a.P2);       \
-  }
-  switch (a.D) {
-    case 1: PO_REFINE(1); break;
-    case 2: PO_REFINE(2); break;
-    default: PO_REFINE(3); break;
-  }
-#undef PO_REFINE
+  const int rc = with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) {
+    static bool attr = false;  // per instance
+    if (!attr) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(grid_refine_build_kernel<D>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return check_launch("grid refine attribute");
+      attr = true;
+    }
+    hipLaunchKernelGGL((grid_refine_build_kernel<D>), grid, dim3(kRefineBlock), lds, a.stream, ws, a.P2);
+    return POINTOPS_OK;
+  });
+  if (rc != POINTOPS_OK) return rc;
   return check_launch("grid refine");
 }
 

@@ -173,45 +173,6 @@ __global__ __launch_bounds__(kKnnBlock) void knn_generic_kernel(
 // ---------------------------------------------------------------------------
 // host dispatch
 // ---------------------------------------------------------------------------
-struct RegLaunch {
-  int block, tiles, S;
-  unsigned long long* partial;
-};
-
-template <int D, int KC, int NORM>
-static void launch_reg(const KnnArgs& a, const RegLaunch& r) {
-  const dim3 grid((unsigned)(a.N * r.tiles), (unsigned)r.S);
-  hipLaunchKernelGGL((knn_reg_kernel<D, KC, NORM>), grid, dim3(r.block), 0, a.stream, a.p1, a.p2, a.l1, a.l2, a.P1,
-                     a.P2, a.K, r.tiles, a.qlist, a.qcount, r.S, r.partial, a.idxs, a.dists);
-}
-
-template <int D, int NORM>
-static void dispatch_k(const KnnArgs& a, const RegLaunch& r) {
-  const int K = a.K;
-  if (K <= 1) launch_reg<D, 1, NORM>(a, r);
-  else if (K <= 2) launch_reg<D, 2, NORM>(a, r);
-  else if (K <= 4) launch_reg<D, 4, NORM>(a, r);
-  else if (K <= 8) launch_reg<D, 8, NORM>(a, r);
-  else if (K <= 16) launch_reg<D, 16, NORM>(a, r);
-  else if (K <= 24) launch_reg<D, 24, NORM>(a, r);
-  else launch_reg<D, 32, NORM>(a, r);
-}
-
-template <int NORM>
-static void dispatch_d(const KnnArgs& a, const RegLaunch& r) {
-  switch (a.D) {
-    case 1: dispatch_k<1, NORM>(a, r); break;
-    case 2: dispatch_k<2, NORM>(a, r); break;
-    case 3: dispatch_k<3, NORM>(a, r); break;
-    case 4: dispatch_k<4, NORM>(a, r); break;
-    case 5: dispatch_k<5, NORM>(a, r); break;
-    case 6: dispatch_k<6, NORM>(a, r); break;
-    case 7: dispatch_k<7, NORM>(a, r); break;
-    case 8: dispatch_k<8, NORM>(a, r); break;
-    default: break;
-  }
-}
-
 // p2 slices per query so that a small batch still fills the chip (1024 SIMDs)
 static int knn_split_count(int64_t N, int64_t P1, int64_t P2, int64_t K) {
   if (K > 32) return 1;
@@ -228,33 +189,34 @@ void knn_merge_partials(const KnnArgs& a, int S, const void* workspace) {
   const int64_t total = a.N * a.P1;
   const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
   const unsigned long long* ws = (const unsigned long long*)workspace;
-#define PO_MERGE(KC)                                                                                              \
-  hipLaunchKernelGGL(knn_merge_kernel<KC>, grid, block, 0, a.stream, ws, a.l1, a.l2, a.P1, a.P2, a.K, S, total, \
-                     a.idxs, a.dists)
-  const int K = a.K;
-  if (K <= 1) PO_MERGE(1);
-  else if (K <= 2) PO_MERGE(2);
-  else if (K <= 4) PO_MERGE(4);
-  else if (K <= 8) PO_MERGE(8);
-  else if (K <= 16) PO_MERGE(16);
-  else if (K <= 24) PO_MERGE(24);
-  else PO_MERGE(32);
-#undef PO_MERGE
+  with_bucket(kScanKC, a.K, [&](auto KC) {
+    hipLaunchKernelGGL(knn_merge_kernel<KC>, grid, block, 0, a.stream, ws, a.l1, a.l2, a.P1, a.P2, a.K, S, total, a.idxs,
+                       a.dists);
+  });
 }
 
 void launch_knn_bruteforce(const KnnArgs& a, int norm, int splits, void* workspace) {
   // small batches: 64-lane workgroups (4x as many) and p2 slices; the query-list mode of the grid
   // fallback always scans whole clouds
-  RegLaunch r{kKnnBlock, a.tiles, 1, nullptr};
+  int block = kKnnBlock, tiles = a.tiles, S = 1;
+  unsigned long long* partial = nullptr;
   if (a.qlist == nullptr && a.N * a.tiles < 2048) {
-    r.block = 64;
-    r.tiles = (int)ceil_div(a.P1, 64);
-    r.S = splits;
-    r.partial = (unsigned long long*)workspace;
+    block = 64;
+    tiles = (int)ceil_div(a.P1, 64);
+    S = splits;
+    partial = (unsigned long long*)workspace;
   }
-  if (norm == 1) dispatch_d<1>(a, r);
-  else dispatch_d<2>(a, r);
-  if (r.S > 1) knn_merge_partials(a, r.S, workspace);
+  const dim3 grid((unsigned)(a.N * tiles), (unsigned)S);
+  with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+    with_exact<0>(kScanD, a.D, [&](auto D) {
+      if constexpr (D != 0)  // (any other D has no instance: nothing is launched)
+        with_bucket(kScanKC, a.K, [&](auto KC) {
+          hipLaunchKernelGGL((knn_reg_kernel<D, KC, NORM>), grid, dim3(block), 0, a.stream, a.p1, a.p2, a.l1, a.l2, a.P1,
+                             a.P2, a.K, tiles, a.qlist, a.qcount, S, partial, a.idxs, a.dists);
+        });
+    });
+  });
+  if (S > 1) knn_merge_partials(a, S, workspace);
 }
 
 static int choose_version(int version, int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K) {
@@ -362,12 +324,10 @@ int pointops_knn_points_idx_reuse(const float* p1, const float* p2, const int64_
     case KnnFamily::kWide: rc = launch_knn_wide(a, norm, plan.splits, workspace); break;
     case KnnFamily::kGeneric: {
       const dim3 grid((unsigned)(N * a.tiles));
-      if (norm == 1)
-        hipLaunchKernelGGL(knn_generic_kernel<1>, grid, dim3(kKnnBlock), 0, a.stream, p1, p2, lengths1,
-                           lengths2, a.P1, a.P2, a.D, a.K, a.tiles, idxs, dists);
-      else
-        hipLaunchKernelGGL(knn_generic_kernel<2>, grid, dim3(kKnnBlock), 0, a.stream, p1, p2, lengths1,
-                           lengths2, a.P1, a.P2, a.D, a.K, a.tiles, idxs, dists);
+      with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+        hipLaunchKernelGGL(knn_generic_kernel<NORM>, grid, dim3(kKnnBlock), 0, a.stream, p1, p2, lengths1, lengths2,
+                           a.P1, a.P2, a.D, a.K, a.tiles, idxs, dists);
+      });
       break;
     }
     case KnnFamily::kSmall: launch_knn_small(a, norm); break;

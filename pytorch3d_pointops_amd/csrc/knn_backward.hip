@@ -271,56 +271,35 @@ extern "C" int pointops_knn_points_backward(const float* p1, const float* p2,
     const int tiles4 = (int)ceil_div(P1 * 4, kBwdBlock);
     POINTOPS_REQUIRE(N * tiles4 < (1LL << 31), "knn_points_backward: grid too large");
     const dim3 grid4((unsigned)(N * tiles4)), block4(kBwdBlock);
-#define PO_LAUNCH4(NORM, SCATTER)                                                                               \
-  hipLaunchKernelGGL((knn_backward4_kernel<NORM, SCATTER>), grid4, block4, 0, stream, p1, p2, lengths1, lengths2, \
-                     idxs, grad_dists, (int)P1, (int)P2, (int)D, (int)K, tiles4, grad_p1, grad_p2)
     if (!tiled) {
-      if (norm == 1) PO_LAUNCH4(1, true);
-      else PO_LAUNCH4(2, true);
+      with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+        hipLaunchKernelGGL((knn_backward4_kernel<NORM, true>), grid4, block4, 0, stream, p1, p2, lengths1, lengths2,
+                           idxs, grad_dists, (int)P1, (int)P2, (int)D, (int)K, tiles4, grad_p1, grad_p2);
+      });
       return check_launch("knn_points_backward");
     }
-#undef PO_LAUNCH4
     const int tiles = (int)ceil_div(P1, kBwdBlock);
     const dim3 gridr((unsigned)(N * tiles)), blockr(kBwdBlock);
     const DivMagic dm = division_magic((unsigned)K);
-#define PO_TILED(DT, NORM)                                                                                     \
-  do {                                                                                                         \
-    hipLaunchKernelGGL((knn_backward_rows_kernel<DT, NORM>), gridr, blockr, 0, stream, p1, p2, lengths1,       \
-                       lengths2, idxs, grad_dists, (int)P1, (int)P2, (int)K, tiles, grad_p1);                  \
-    const KnnGradSrc<DT, NORM> src{p1, p2, lengths1, lengths2, grad_dists, (int)P1, (int)P2, (int)K};          \
-    hipLaunchKernelGGL((tiled_scatter_kernel<KnnGradSrc<DT, NORM>>), plan.grid, dim3(kTiledBlock), 0, stream,  \
-                       src, idxs, (int)N, (int)P1, (int)P2, (int)K, dm, plan.parts, S, grad_p2);               \
-  } while (0)
-    if (norm == 1) {
-      if (D == 1) PO_TILED(1, 1);
-      else if (D == 2) PO_TILED(2, 1);
-      else if (D == 3) PO_TILED(3, 1);
-      else PO_TILED(4, 1);
-    } else {
-      if (D == 1) PO_TILED(1, 2);
-      else if (D == 2) PO_TILED(2, 2);
-      else if (D == 3) PO_TILED(3, 2);
-      else PO_TILED(4, 2);
-    }
-#undef PO_TILED
+    with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+      with_exact<4>(Ints<1, 2, 3>{}, (int)D, [&](auto DT) {
+        hipLaunchKernelGGL((knn_backward_rows_kernel<DT, NORM>), gridr, blockr, 0, stream, p1, p2, lengths1, lengths2,
+                           idxs, grad_dists, (int)P1, (int)P2, (int)K, tiles, grad_p1);
+        const KnnGradSrc<DT, NORM> src{p1, p2, lengths1, lengths2, grad_dists, (int)P1, (int)P2, (int)K};
+        hipLaunchKernelGGL((tiled_scatter_kernel<KnnGradSrc<DT, NORM>>), plan.grid, dim3(kTiledBlock), 0, stream, src,
+                           idxs, (int)N, (int)P1, (int)P2, (int)K, dm, plan.parts, S, grad_p2);
+      });
+    });
     return check_launch("knn_points_backward(tiled)");
   }
   const int tiles = (int)ceil_div(P1, kBwdBlock);
   POINTOPS_REQUIRE(N * tiles < (1LL << 31), "knn_points_backward: grid too large");
   const dim3 grid((unsigned)(N * tiles)), block(kBwdBlock);
-#define PO_LAUNCH(DT, NORM)                                                                       \
-  hipLaunchKernelGGL((knn_backward_kernel<DT, NORM>), grid, block, 0, stream, p1, p2, lengths1,   \
-                     lengths2, idxs, grad_dists, (int)P1, (int)P2, (int)D, (int)K, tiles, grad_p1, \
-                     grad_p2)
-  if (norm == 1) {
-    if (D == 3) PO_LAUNCH(3, 1);
-    else if (D == 2) PO_LAUNCH(2, 1);
-    else PO_LAUNCH(0, 1);
-  } else {
-    if (D == 3) PO_LAUNCH(3, 2);
-    else if (D == 2) PO_LAUNCH(2, 2);
-    else PO_LAUNCH(0, 2);
-  }
-#undef PO_LAUNCH
+  with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+    with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
+      hipLaunchKernelGGL((knn_backward_kernel<DT, NORM>), grid, block, 0, stream, p1, p2, lengths1, lengths2, idxs,
+                         grad_dists, (int)P1, (int)P2, (int)D, (int)K, tiles, grad_p1, grad_p2);
+    });
+  });
   return check_launch("knn_points_backward");
 }

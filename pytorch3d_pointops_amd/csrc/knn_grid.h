@@ -27,6 +27,11 @@ struct KnnPlan {
 };
 KnnPlan knn_plan(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K, int version);
 
+// the register scan's instances (knn.hip, knn_small.hip): D in [1, 8], list capacities KC >= K; the merge of its
+// partial lists takes the same KC
+constexpr Ints<1, 2, 3, 4, 5, 6, 7, 8> kScanD{};
+constexpr Ints<1, 2, 4, 8, 16, 24, 32> kScanKC{};
+
 // brute-force register-top-K scan (knn.hip); honours a.qlist / a.qcount.  With splits > 1 (the plan's, and a
 // `workspace` of its bytes) a small batch is scanned in p2 slices and merged.
 void launch_knn_bruteforce(const KnnArgs& a, int norm, int splits = 1, void* workspace = nullptr);

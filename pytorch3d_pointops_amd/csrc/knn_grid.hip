@@ -37,8 +37,8 @@
 
 namespace pointops {
 
-// list capacity of the search kernels (sorting networks exist for powers of two)
-static int grid_kc(int K) { return K <= 1 ? 1 : K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64; }
+// the search kernels' list capacity for K
+static int grid_kc(int K) { return with_bucket(kGridKC, K, [](auto KC) { return KC.value; }); }
 
 static float knn_cell_target(int K) {
   // the search keeps the KC >= K best but certifies the K-th, so the cells are sized for K points:
@@ -99,11 +99,9 @@ static int knn_grid_run_slice(const KnnArgs& a, int norm, void* workspace, int r
   const bool quad = kc <= 32 && grid_quad_mode(a.N * (int64_t)a.P1, kc);  // (64-slot lists: four of them do not fit a quad's registers)
   // run words of the lane / box searches: 21-bit record indices, or 24-bit ones for the biggest clouds
   const bool big = a.P2 > kGridMaxPoints || debug_knob("grid_big", 0) != 0;
-  switch (a.D) {
-    case 1: (big ? grid_search_d1w : grid_search_d1)(a, ws, norm, kc, quad); break;
-    case 2: (big ? grid_search_d2w : grid_search_d2)(a, ws, norm, kc, quad); break;
-    default: (big ? grid_search_d3w : grid_search_d3)(a, ws, norm, kc, quad); break;
-  }
+  with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) {
+    (big ? grid_search<D, kRunBitsBig> : grid_search<D, kRunBitsStd>)(a, ws, norm, kc, quad);
+  });
   rc = check_launch("knn_points_idx(grid)");
   if (rc != POINTOPS_OK) return rc;
   // exact fallback: whole-cloud scan for the queries the bound could not certify

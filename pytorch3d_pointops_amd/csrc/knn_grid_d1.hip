@@ -4,9 +4,6 @@
 
 namespace pointops {
 
-void grid_search_d1(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad) {
-  if (norm == 1) grid_search_dispatch<1, 1, kRunBitsStd>(a, ws, kc, quad);
-  else grid_search_dispatch<1, 2, kRunBitsStd>(a, ws, kc, quad);
-}
+template void grid_search<1, kRunBitsStd>(const KnnArgs&, const GridWs&, int, int, bool);
 
 }  // namespace pointops

@@ -4,9 +4,6 @@
 
 namespace pointops {
 
-void grid_search_d3(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad) {
-  if (norm == 1) grid_search_dispatch<3, 1, kRunBitsStd>(a, ws, kc, quad);
-  else grid_search_dispatch<3, 2, kRunBitsStd>(a, ws, kc, quad);
-}
+template void grid_search<3, kRunBitsStd>(const KnnArgs&, const GridWs&, int, int, bool);
 
 }  // namespace pointops

@@ -5,9 +5,6 @@
 
 namespace pointops {
 
-void grid_search_d3w(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad) {
-  if (norm == 1) grid_search_dispatch<3, 1, kRunBitsBig>(a, ws, kc, quad);
-  else grid_search_dispatch<3, 2, kRunBitsBig>(a, ws, kc, quad);
-}
+template void grid_search<3, kRunBitsBig>(const KnnArgs&, const GridWs&, int, int, bool);
 
 }  // namespace pointops

@@ -701,26 +701,26 @@ static void launch_grid_passes(const KnnArgs& a, const GridWs& ws, bool quad) {
                      ws.fb2_count, ws.fb2_list, ws.cell_cap, a.P1, a.P2, a.K, quad ? 4 : 2, a.idxs, a.dists);
 }
 
-template <int D, int NORM, int RB>
-void grid_search_dispatch(const KnnArgs& a, const GridWs& ws, int kc, bool quad) {
-  switch (kc) {
-    case 1: launch_grid_passes<D, 1, NORM, RB>(a, ws, quad); break;
-    case 2: launch_grid_passes<D, 2, NORM, RB>(a, ws, quad); break;
-    case 4: launch_grid_passes<D, 4, NORM, RB>(a, ws, quad); break;
-    case 8: launch_grid_passes<D, 8, NORM, RB>(a, ws, quad); break;
-    case 16: launch_grid_passes<D, 16, NORM, RB>(a, ws, quad); break;
-    case 32: launch_grid_passes<D, 32, NORM, RB>(a, ws, quad); break;
-    default: launch_grid_passes<D, 64, NORM, RB>(a, ws, false); break;
-  }
+// list capacities of the search kernels (sorting networks exist for powers of two): the smallest KC >= K
+constexpr Ints<1, 2, 4, 8, 16, 32, 64> kGridKC{};
+
+// all passes of one (D, run-word geometry) for the list capacity kc (a kGridKC value)
+template <int D, int RB>
+void grid_search(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad) {
+  with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+    with_bucket(kGridKC, kc, [&](auto KC) {
+      launch_grid_passes<D, KC, NORM, RB>(a, ws, KC <= 32 && quad);  // (64-slot lists never take the quad pass)
+    });
+  });
 }
 
-// one translation unit per point dimension and run-word geometry (knn_grid_d1/2/3.hip: clouds of up to
-// kGridMaxPoints points; knn_grid_d1/2/3w.hip: bigger ones)
-void grid_search_d1(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad);
-void grid_search_d2(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad);
-void grid_search_d3(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad);
-void grid_search_d1w(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad);
-void grid_search_d2w(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad);
-void grid_search_d3w(const KnnArgs& a, const GridWs& ws, int norm, int kc, bool quad);
+// one translation unit per instance (knn_grid_d1/2/3.hip: clouds of up to kGridMaxPoints points; knn_grid_d1/2/3w.hip:
+// bigger ones)
+extern template void grid_search<1, kRunBitsStd>(const KnnArgs&, const GridWs&, int, int, bool);
+extern template void grid_search<2, kRunBitsStd>(const KnnArgs&, const GridWs&, int, int, bool);
+extern template void grid_search<3, kRunBitsStd>(const KnnArgs&, const GridWs&, int, int, bool);
+extern template void grid_search<1, kRunBitsBig>(const KnnArgs&, const GridWs&, int, int, bool);
+extern template void grid_search<2, kRunBitsBig>(const KnnArgs&, const GridWs&, int, int, bool);
+extern template void grid_search<3, kRunBitsBig>(const KnnArgs&, const GridWs&, int, int, bool);
 
 }  // namespace pointops

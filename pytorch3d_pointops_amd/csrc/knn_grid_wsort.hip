@@ -228,20 +228,14 @@ void grid_search_wsort(const KnnArgs& a, const GridWs& ws, int norm) {
   const int64_t cap = (int64_t)(65536 / (a.N > 0 ? a.N : 1));  // ~16 resident waves per SIMD-slot's worth of queries per cloud
   wx = wx > cap ? (cap < 64 ? 64 : cap) : wx;
   const dim3 grid((unsigned)wx, (unsigned)a.N);
-#define PO_WS(DD, NN)                                                                                               \
-  hipLaunchKernelGGL((knn_grid_wsort_kernel<DD, NN>), grid, dim3(kWsBlock), 0, a.stream, a.p1, (const GridCloud*)ws.cloud, \
-                     (const float*)ws.edges, (const int*)ws.cell_start, (const float4*)ws.sorted, ws.fb2_count,      \
-                     ws.fb2_list, ws.cell_cap, a.P1, a.P2, a.K, a.idxs, a.dists)
-  if (norm == 1) {
-    if (a.D == 1) PO_WS(1, 1);
-    else if (a.D == 2) PO_WS(2, 1);
-    else PO_WS(3, 1);
-  } else {
-    if (a.D == 1) PO_WS(1, 2);
-    else if (a.D == 2) PO_WS(2, 2);
-    else PO_WS(3, 2);
-  }
-#undef PO_WS
+  with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+    with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) {
+      hipLaunchKernelGGL((knn_grid_wsort_kernel<D, NORM>), grid, dim3(kWsBlock), 0, a.stream, a.p1,
+                         (const GridCloud*)ws.cloud, (const float*)ws.edges, (const int*)ws.cell_start,
+                         (const float4*)ws.sorted, ws.fb2_count, ws.fb2_list, ws.cell_cap, a.P1, a.P2, a.K, a.idxs,
+                         a.dists);
+    });
+  });
 }
 
 }  // namespace pointops

@@ -181,33 +181,6 @@ static void launch_small(const KnnArgs& a) {
   else launch_small_q<D, KC, NORM, 1>(a, qw);
 }
 
-template <int D, int NORM>
-static void small_k(const KnnArgs& a) {
-  const int K = a.K;
-  if (K <= 1) launch_small<D, 1, NORM>(a);
-  else if (K <= 2) launch_small<D, 2, NORM>(a);
-  else if (K <= 4) launch_small<D, 4, NORM>(a);
-  else if (K <= 8) launch_small<D, 8, NORM>(a);
-  else if (K <= 16) launch_small<D, 16, NORM>(a);
-  else if (K <= 24) launch_small<D, 24, NORM>(a);
-  else launch_small<D, 32, NORM>(a);
-}
-
-template <int NORM>
-static void small_d(const KnnArgs& a) {
-  switch (a.D) {
-    case 1: small_k<1, NORM>(a); break;
-    case 2: small_k<2, NORM>(a); break;
-    case 3: small_k<3, NORM>(a); break;
-    case 4: small_k<4, NORM>(a); break;
-    case 5: small_k<5, NORM>(a); break;
-    case 6: small_k<6, NORM>(a); break;
-    case 7: small_k<7, NORM>(a); break;
-    case 8: small_k<8, NORM>(a); break;
-    default: break;
-  }
-}
-
 // Few queries: fewer query WAVES of the lane-per-query scan than the chip has SIMDs x 2 (x 0.5 for lists beyond 16 slots,
 // whose inserts and extraction cost more here): tools/knn_small_sweep.py, profiles/r03_knn_small_sweep.jsonl.
 // POINTOPS_DEBUG knn_small=0 keeps the sliced scan, =1 takes every batch the kernel supports (tests).
@@ -220,8 +193,12 @@ bool knn_small_applies(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K) 
 }
 
 void launch_knn_small(const KnnArgs& a, int norm) {
-  if (norm == 1) small_d<1>(a);
-  else small_d<2>(a);
+  with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+    with_exact<0>(kScanD, a.D, [&](auto D) {
+      if constexpr (D != 0)  // (any other D has no instance: nothing is launched)
+        with_bucket(kScanKC, a.K, [&](auto KC) { launch_small<D, KC, NORM>(a); });
+    });
+  });
 }
 
 }  // namespace pointops

@@ -281,25 +281,22 @@ int launch_knn_wide(const KnnArgs& a, int norm, int splits, void* workspace) {
   const int K = a.K;
   if (K <= 32) {
     // 64-lane workgroups while the batch is small (4x the workgroups), 256 lanes otherwise
-    const int S = splits;
-    const bool small = a.N * ceil_div(a.P1, 256) < 2048;
-    const size_t lds = (size_t)a.D * (small ? 64 : 256) * 4;
-#define PO_WIDE(KC)                                                                                                 \
-  return small ? (norm == 1 ? launch_wide<KC, 1, 64>(a, lds, S, workspace) : launch_wide<KC, 2, 64>(a, lds, S, workspace)) \
-               : (norm == 1 ? launch_wide<KC, 1, 256>(a, lds, 1, workspace) : launch_wide<KC, 2, 256>(a, lds, 1, workspace))
-    if (K <= 4) PO_WIDE(4);
-    else if (K <= 8) PO_WIDE(8);
-    else if (K <= 16) PO_WIDE(16);
-    else if (K <= 24) PO_WIDE(24);
-    else PO_WIDE(32);
-#undef PO_WIDE
+    const int wg = a.N * ceil_div(a.P1, 256) < 2048 ? 64 : 256;
+    const size_t lds = (size_t)a.D * wg * 4;
+    return with_bucket(Ints<4, 8, 16, 24, 32>{}, K, [&](auto KC) {
+      return with_exact<256>(Ints<64>{}, wg, [&](auto WG) {
+        return with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+          return launch_wide<KC, NORM, WG>(a, lds, WG == 64 ? splits : 1, workspace);
+        });
+      });
+    });
   }
   if (K <= kLongKC) {
     const size_t lds = ((size_t)a.D * 4 + (size_t)kLongQueue * 8) * 64;
-    return norm == 1 ? launch_wide<kLongKC, 1, 64>(a, lds, 1, workspace) : launch_wide<kLongKC, 2, 64>(a, lds, 1, workspace);
+    return with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) { return launch_wide<kLongKC, NORM, 64>(a, lds, 1, workspace); });
   }
   const size_t lds = ((size_t)a.D * 4 + (size_t)K * 8) * 64;
-  return norm == 1 ? launch_wide<0, 1, 64>(a, lds, 1, workspace) : launch_wide<0, 2, 64>(a, lds, 1, workspace);
+  return with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) { return launch_wide<0, NORM, 64>(a, lds, 1, workspace); });
 }
 
 }  // namespace pointops
