@@ -296,6 +296,31 @@ int pointops_point_covariances(const float* knn, int64_t N, int64_t P, int64_t K
 int pointops_point_covariances_backward(const float* knn, const float* grad_cov, int64_t N, int64_t P, int64_t K,
                                         int64_t D, float* grad_knn, void* stream);
 
+/*
+ * Per-point curvatures and local coordinate frames of a K-neighbourhood, fused -- device half of
+ * estimate_pointcloud_local_coord_frames / estimate_pointcloud_normals (PyTorch3D's ops/points_normals.py; the
+ * reference package has only the covariance, functions/utils.py:111-153, and leaves the rest to torch).
+ *   points (N,P,3) fp32, lengths (N,), idx (N,P,K) int64 (knn_points of points against itself), K >= 1.
+ *   For every row i < lengths[n]: the neighbours x_k = points[n, idx[n,i,k]] (zero where k >= lengths[n] or idx is
+ *   outside [0,P)), C = mean_k (x_k - m)(x_k - m)^T with m = mean_k x_k -- bit-equal to pointops_point_covariances
+ *   of pointops_gather_neighbors(points, idx, lengths) --, then its eigen-decomposition (fp64 cyclic Jacobi, rounded
+ *   to fp32): curvatures (N,P,3) = eigenvalues ascending, frames (N,P,3,3) with column j = unit eigenvector j.
+ *   disambiguate != 0: columns 0 (n) and 2 (z) are negated when fewer than K/2 neighbours have (x_k - x_i).v > 0
+ *   (x_i = points[n,i]), and column 1 becomes n x z.  Otherwise the eigenvector signs are implementation-defined.
+ *   Rows i >= lengths[n] are zero in both outputs; a zero C gives zero curvatures and the identity frame (before
+ *   disambiguation).  No atomics (deterministic), no workspace.  N < 65536.
+ * Backward: grad_cov (N,P,3,3) from the saved outputs and their gradients (N,P,3), (N,P,3,3) -- with disambiguate,
+ *   y = n x z is folded into n and z first; then grad_C = sum_i g_i v_i v_i^T
+ *   + sum_{i != j} (v_j . grad_v_i) / (lambda_i - lambda_j) v_j v_i^T.  Rows i >= lengths[n] get 0.  Coincident
+ *   eigenvalues divide by zero (inf / nan), as torch.linalg.eigh's backward does.  The gradient of the points follows
+ *   through pointops_gather_neighbors, pointops_point_covariances_backward and pointops_gather_neighbors_backward.
+ */
+int pointops_local_frames(const float* points, const int64_t* lengths, const int64_t* idx, int64_t N, int64_t P,
+                          int64_t K, int disambiguate, float* curvatures, float* frames, void* stream);
+int pointops_local_frames_backward(const float* curvatures, const float* frames, const float* grad_curvatures,
+                                   const float* grad_frames, const int64_t* lengths, int64_t N, int64_t P,
+                                   int disambiguate, float* grad_cov, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

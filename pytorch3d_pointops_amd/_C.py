@@ -59,6 +59,8 @@ _SIGNATURES = {
     "pointops_sample_pdf": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp]),
     "pointops_point_covariances": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "pointops_point_covariances_backward": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "pointops_local_frames": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "pointops_local_frames_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp]),
     "pointops_chamfer_workspace_bytes": (_sz, [_i64, _i64]),
     "pointops_chamfer_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int,
                                         _int, _vp, _vp, _sz, _vp]),
@@ -505,6 +507,44 @@ def point_covariances_backward(knn, grad_cov):
                                                         grad_knn.data_ptr(), _stream()),
                "point_covariances_backward")
     return grad_knn
+
+
+# --- fused local frames of functions/points_normals.py (csrc/local_frames.hip) -------
+def local_frames(points, lengths, idx, disambiguate: bool):
+    """points (N,P,3) fp32, lengths (N,), idx (N,P,K) -> curvatures (N,P,3), frames (N,P,3,3)."""
+    dev = _require_gpu(points, lengths, idx)
+    points, lengths, idx = _f32c(points, "points"), _i64c(lengths, "lengths"), _i64c(idx, "idx")
+    N, P, D = points.shape
+    if D != 3 or idx.dim() != 3 or idx.shape[:2] != (N, P) or lengths.shape != (N,):
+        raise RuntimeError("local_frames: need points (N,P,3), lengths (N,) and idx (N,P,K)")
+    with _on(dev):
+        curvatures = torch.empty((N, P, 3), dtype=torch.float32, device=dev)
+        frames = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
+        _check(_lib.pointops_local_frames(points.data_ptr(), lengths.data_ptr(), idx.data_ptr(), N, P, idx.shape[2],
+                                          int(bool(disambiguate)), curvatures.data_ptr(), frames.data_ptr(),
+                                          _stream()),
+               "local_frames")
+    return curvatures, frames
+
+
+def local_frames_backward(curvatures, frames, grad_curvatures, grad_frames, lengths, disambiguate: bool):
+    """-> grad_cov (N,P,3,3), the gradient of the per-point covariance (csrc/local_frames.hip)."""
+    dev = _require_gpu(curvatures, frames, grad_curvatures, grad_frames, lengths)
+    curvatures, frames = _f32c(curvatures, "curvatures"), _f32c(frames, "frames")
+    grad_curvatures, grad_frames = _f32c(grad_curvatures, "grad_curvatures"), _f32c(grad_frames, "grad_frames")
+    lengths = _i64c(lengths, "lengths")
+    N, P = curvatures.shape[:2]
+    if (curvatures.shape != (N, P, 3) or grad_curvatures.shape != (N, P, 3) or frames.shape != (N, P, 3, 3)
+            or grad_frames.shape != (N, P, 3, 3) or lengths.shape != (N,)):
+        raise RuntimeError("local_frames_backward: inconsistent shapes")
+    with _on(dev):
+        grad_cov = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
+        _check(_lib.pointops_local_frames_backward(curvatures.data_ptr(), frames.data_ptr(),
+                                                   grad_curvatures.data_ptr(), grad_frames.data_ptr(),
+                                                   lengths.data_ptr(), N, P, int(bool(disambiguate)),
+                                                   grad_cov.data_ptr(), _stream()),
+               "local_frames_backward")
+    return grad_cov
 
 
 # --- device halves of knn_gather / masked_gather (functions/knn.py:200-250) -------

@@ -202,6 +202,49 @@ point_covariances.register_autograd(
     setup_context=lambda ctx, inputs, output: ctx.save_for_backward(inputs[0].contiguous()))
 
 
+# --------------------------------------------------------------------------- local frames (normals)
+@_op(f"{NS}::local_frames", mutates_args=())
+def local_frames(points: Tensor, lengths: Tensor, idx: Tensor, disambiguate: bool) -> Tuple[Tensor, Tensor]:
+    return _C.local_frames(points, lengths, idx, disambiguate)
+
+
+@local_frames.register_fake
+def _(points, lengths, idx, disambiguate):
+    N, P = points.shape[:2]
+    return _like(points, (N, P, 3), torch.float32), _like(points, (N, P, 3, 3), torch.float32)
+
+
+@_op(f"{NS}::local_frames_backward", mutates_args=())
+def local_frames_backward(curvatures: Tensor, frames: Tensor, grad_curvatures: Tensor, grad_frames: Tensor,
+                          lengths: Tensor, disambiguate: bool) -> Tensor:
+    return _C.local_frames_backward(curvatures, frames, grad_curvatures, grad_frames, lengths, disambiguate)
+
+
+@local_frames_backward.register_fake
+def _(curvatures, frames, grad_curvatures, grad_frames, lengths, disambiguate):
+    return _like(frames, frames.shape, torch.float32)
+
+
+def _local_frames_setup(ctx, inputs, output):
+    points, lengths, idx, disambiguate = inputs
+    ctx.save_for_backward(points, lengths, idx, *output)
+    ctx.disambiguate = disambiguate
+
+
+def _local_frames_grad(ctx, grad_curvatures, grad_frames):
+    # grad_C from the eigenpairs, then the existing covariance chain: gather -> covariance backward -> scatter
+    points, lengths, idx, curvatures, frames = ctx.saved_tensors
+    gl = torch.zeros_like(curvatures) if grad_curvatures is None else grad_curvatures.float().contiguous()
+    gf = torch.zeros_like(frames) if grad_frames is None else grad_frames.float().contiguous()
+    grad_cov = local_frames_backward(curvatures, frames, gl, gf, lengths, ctx.disambiguate)
+    knn = gather_neighbors(points, idx, lengths)
+    grad_knn = point_covariances_backward(knn, grad_cov)
+    return gather_neighbors_backward(grad_knn, idx, lengths, points.shape[1]), None, None, None
+
+
+local_frames.register_autograd(_local_frames_grad, setup_context=_local_frames_setup)
+
+
 # --------------------------------------------------------------------------- chamfer
 @_op(f"{NS}::chamfer_reduce", mutates_args=())
 def chamfer_reduce(dists: Tensor, lengths: Tensor, weights: Optional[Tensor], mean: bool) -> Tensor:

@@ -202,6 +202,23 @@ class Pointclouds:
         """One feature padded to (N, max P_n, C), or None (reference :591)."""
         return self.features_padded().get(name)
 
+    def estimate_normals(self, neighborhood_size: int = 50, disambiguate_directions: bool = True,
+                         assign_to_self: bool = False) -> torch.Tensor:
+        """Padded (N, max P_n, 3) normals of every point from its `neighborhood_size` nearest neighbours
+        (functions.estimate_pointcloud_normals); with `assign_to_self` they also become the padded feature
+        "normals", replacing any existing one (PyTorch3D's Pointclouds.estimate_normals)."""
+        from ..functions.points_normals import estimate_pointcloud_normals
+
+        normals = estimate_pointcloud_normals(self, neighborhood_size=neighborhood_size,
+                                              disambiguate_directions=disambiguate_directions)
+        if assign_to_self:
+            for views in (self._feat_list, self._feat_packed):
+                views.pop("normals", None)
+            self._feat_padded["normals"] = normals
+            if "normals" not in self._feature_names:
+                self._feature_names.append("normals")
+        return normals
+
     # ------------------------------------------------------------------ single clouds, copies of clouds
     def get_cloud(self, index: int):
         """(points (P, 3), {name: (P, C)}) of one cloud (reference :938)."""
