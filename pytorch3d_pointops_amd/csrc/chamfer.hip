@@ -243,11 +243,14 @@ __global__ __launch_bounds__(kCfBlock) void chamfer_backward_kernel(
 #pragma unroll
     for (int c = 0; c < kCfMaxC; ++c) {
       if (c < C) {
-        // dcos/dx1 = (x2n - cos * x1n) / |x1| when |x1| > eps, x2n / eps otherwise (clamped norm)
-        const float gx = b * ix * (nx > eps ? (yn[c] - cosv * xn[c]) : yn[c]);
+        // dcos/dx1 = (x2n - cos * x1n) / |x1| when |x1| > eps; in the clamped band ATen's gradient still has the term
+        // through |x1|: x2n / eps - cos * x1n / |x1| (x2n / eps at x1 = 0)
+        const float gx = nx > eps ? b * ix * (yn[c] - cosv * xn[c])
+                                  : b * (yn[c] * ix - (nx > 0.0f ? cosv * xn[c] / nx : 0.0f));
         cf_put(ft.gx[f] + row * C + c, gx, acc);
         if (y_valid) {
-          const float gy = b * iy * (ny > eps ? (xn[c] - cosv * yn[c]) : xn[c]);
+          const float gy = ny > eps ? b * iy * (xn[c] - cosv * yn[c])
+                                    : b * (xn[c] * iy - (ny > 0.0f ? cosv * yn[c] / ny : 0.0f));
           if (gy != 0.0f) atomicAdd(ft.gy[f] + yrow * C + c, gy);
         }
       }
@@ -338,9 +341,11 @@ __global__ __launch_bounds__(kCfBlock) void chamfer_backward4_kernel(
         xc = (k == c) ? xv[k] : xc;
         yc = (k == c) ? yv[k] : yc;
       }
-      cf_put(ft.gx[f] + row * C + c, b * ix * (nx > eps ? (yc - cosv * xc) : yc), acc);
+      // (clamped band: as in chamfer_backward_kernel)
+      cf_put(ft.gx[f] + row * C + c,
+             nx > eps ? b * ix * (yc - cosv * xc) : b * (yc * ix - (nx > 0.0f ? cosv * xc / nx : 0.0f)), acc);
       if (y_valid) {
-        const float gy = b * iy * (ny > eps ? (xc - cosv * yc) : xc);
+        const float gy = ny > eps ? b * iy * (xc - cosv * yc) : b * (xc * iy - (ny > 0.0f ? cosv * yc / ny : 0.0f));
         if (gy != 0.0f) atomicAdd(ft.gy[f] + yrow * C + c, gy);
       }
     }
