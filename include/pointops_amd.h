@@ -321,6 +321,53 @@ int pointops_local_frames_backward(const float* curvatures, const float* frames,
                                    const float* grad_frames, const int64_t* lengths, int64_t N, int64_t P,
                                    int disambiguate, float* grad_cov, void* stream);
 
+/*
+ * Alignment of corresponding points (weighted Umeyama / Kabsch), fused -- device half of PyTorch3D's
+ * ops/points_alignment.py `corresponding_points_alignment` (the reference package has no registration at all).
+ *   X (N,P,D), Y (N,P2,D) fp32, D in {2,3}; idx (N,P) int64 or NULL: row i of X corresponds to Y[n, idx[n,i]] (clamped
+ *   into [0,P2)), without idx to Y[n,i] (then P2 == P); lengths (N,) or NULL (= P); weights (N,P) fp32 or NULL (= 1).
+ *   With w_i = weights[n,i] for i < lengths[n] and 0 above, W = max(sum w, eps), xm = sum w x / W, ym likewise,
+ *   C = sum w^2 (x - xm)(y - ym)^T / W = U S V^T:  R (N,D,D) = U E V^T with E = diag(1,..,1, det(U V^T)) (E = I when
+ *   allow_reflection), s (N,) = tr(E S) / max(sum w^2 |x - xm|^2 / W, eps) when estimate_scale, else 1, and
+ *   T (N,D) = ym - s xm R  -- the row-vector convention  X_aligned = s X R + T.
+ *   Sums are fp64 and reduced in a fixed order (no atomics: bit-reproducible); the D x D SVD is a one-sided fp64
+ *   Jacobi on C itself.  A rank-deficient C (collinear or coincident points, an empty cloud) gives a finite
+ *   orthogonal R, the identity for C == 0.
+ *   moments (N, 3+4D+D*D) fp64 or NULL: the reduced sums about the pivots X[n,0], Y[n,0] (what the backward needs);
+ *   singular_values (N,D) fp32 or NULL: S, descending.  workspace: pointops_points_alignment_workspace_bytes(N,P,D).
+ * Backward (without idx): grad_moments (N, 3+4D+D*D) fp64 -> grad_X, grad_Y (N,P,D), grad_weights (N,P) or NULL;
+ *   rows i >= lengths[n] get 0.  The gradient of the moments is the host's business (N tiny solves).
+ */
+size_t pointops_points_alignment_workspace_bytes(int64_t N, int64_t P, int64_t D);
+int pointops_points_alignment(const float* X, const float* Y, const int64_t* idx, const int64_t* lengths,
+                              const float* weights, int64_t N, int64_t P, int64_t P2, int64_t D, int estimate_scale,
+                              int allow_reflection, double eps, float* R, float* T, float* s, double* moments,
+                              float* singular_values, void* workspace, size_t workspace_bytes, void* stream);
+int pointops_points_alignment_backward(const float* X, const float* Y, const int64_t* lengths, const float* weights,
+                                       const double* grad_moments, int64_t N, int64_t P, int64_t D, float* grad_X,
+                                       float* grad_Y, float* grad_weights, void* stream);
+
+/*
+ * One iteration of PyTorch3D's `iterative_closest_point` behind one entry: the K=1, L2 search of Xt (N,P1,D) in
+ * Y (N,P2,D) (pointops_knn_points_idx_reuse, version -1, on `knn_workspace` of pointops_knn_workspace_bytes(N,P1,P2,D,
+ * 1,-1) bytes), the alignment of X_init to Y[idx] weighted by the validity mask of lengths_x (eps 1e-9), Xt = s X_init R
+ * + T (fp32; rows >= lengths_x[n] zero) written IN PLACE over the queries, and
+ *   rmse[n] = sqrt(sum_valid |Xt - Y[idx]|^2 / max(lengths_x[n], 1e-9))       (in: the previous iteration's, out: this one's)
+ *   converged[0] = 1 when (prev - rmse) / prev <= relative_rmse_thr for every cloud, else 0; the change counts as 1
+ *   when `first` != 0 and as 0 where prev == 0 (an empty or exactly matched cloud has nothing left to gain).
+ *   reuse: 0 = build the search structure; 1 = the caller vouches that Y, lengths_y and the shape are those of the
+ *   previous call into knn_workspace (see pointops_knn_points_idx_reuse); -1 = no search, idx (N,P1) is an input.
+ *   idx (N,P1) int64 and dists (N,P1) fp32 are outputs of the search; R, T, s as above.  N, P1, P2 >= 1.
+ *   workspace: pointops_icp_workspace_bytes(N, P1, D).  Nothing synchronises; no floating-point atomics.
+ */
+size_t pointops_icp_workspace_bytes(int64_t N, int64_t P1, int64_t D);
+int pointops_icp_iteration(const float* X_init, float* Xt, const float* Y, const int64_t* lengths_x,
+                           const int64_t* lengths_y, int64_t N, int64_t P1, int64_t P2, int64_t D, int estimate_scale,
+                           int allow_reflection, int first, int reuse, float relative_rmse_thr, int64_t* idx,
+                           float* dists, float* R, float* T, float* s, float* rmse, int32_t* converged,
+                           void* knn_workspace, size_t knn_workspace_bytes, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

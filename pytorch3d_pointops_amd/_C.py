@@ -22,6 +22,7 @@ _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
 _f32 = ctypes.c_float
+_f64 = ctypes.c_double
 _sz = ctypes.c_size_t
 
 # name -> (restype, argtypes); must list every symbol of include/pointops_amd.h
@@ -61,6 +62,13 @@ _SIGNATURES = {
     "pointops_point_covariances_backward": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "pointops_local_frames": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
     "pointops_local_frames_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp]),
+    "pointops_points_alignment_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "pointops_points_alignment": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _f64, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pointops_points_alignment_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pointops_icp_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "pointops_icp_iteration": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _f32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "pointops_chamfer_workspace_bytes": (_sz, [_i64, _i64]),
     "pointops_chamfer_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int,
                                         _int, _vp, _vp, _sz, _vp]),
@@ -545,6 +553,133 @@ def local_frames_backward(curvatures, frames, grad_curvatures, grad_frames, leng
                                                    grad_cov.data_ptr(), _stream()),
                "local_frames_backward")
     return grad_cov
+
+
+# --- fused registration of functions/points_alignment.py (csrc/points_alignment.hip) -------
+POINTS_ALIGNMENT_DIMS = (2, 3)
+
+
+def alignment_moment_count(D: int) -> int:
+    return 3 + 4 * D + D * D
+
+
+def points_alignment(X, Y, idx, lengths, weights, estimate_scale: bool, allow_reflection: bool, eps: float,
+                     want_moments: bool = False):
+    """X (N,P,D), Y (N,P2,D) fp32, idx (N,P) int64 or None (row i of X <-> Y[n, idx[n,i]]; None: Y[n,i]), lengths
+    (N,) or None, weights (N,P) or None -> R (N,D,D), T (N,D), s (N,), singular values (N,D) and, with `want_moments`,
+    the fp64 moments (N, 3+4D+D*D) the backward starts from (else None)."""
+    opt = [t for t in (idx, lengths, weights) if t is not None]
+    dev = _require_gpu(X, Y, *opt)
+    X, Y = _f32c(X, "X"), _f32c(Y, "Y")
+    idx = _i64c(idx, "idx") if idx is not None else None
+    lengths = _i64c(lengths, "lengths") if lengths is not None else None
+    weights = _f32c(weights, "weights") if weights is not None else None
+    if X.dim() != 3 or Y.dim() != 3:
+        raise RuntimeError("points_alignment: X and Y must be 3-dimensional")
+    N, P, D = X.shape
+    P2 = Y.shape[1]
+    if (Y.shape[0] != N or Y.shape[2] != D or D not in POINTS_ALIGNMENT_DIMS or (idx is None and P2 != P)
+            or (idx is not None and idx.shape != (N, P)) or (lengths is not None and lengths.shape != (N,))
+            or (weights is not None and weights.shape != (N, P))):
+        raise RuntimeError("points_alignment: need X (N,P,D), Y (N,P2,D), D in {2,3}, idx (N,P), lengths (N,), "
+                           "weights (N,P)")
+    with _on(dev):
+        R = torch.empty((N, D, D), dtype=torch.float32, device=dev)
+        T = torch.empty((N, D), dtype=torch.float32, device=dev)
+        s = torch.empty((N,), dtype=torch.float32, device=dev)
+        sing = torch.empty((N, D), dtype=torch.float32, device=dev)
+        moments = torch.empty((N, alignment_moment_count(D)), dtype=torch.float64, device=dev) if want_moments else None
+        ws_bytes = _lib.pointops_points_alignment_workspace_bytes(N, P, D)
+        ws = _workspace(ws_bytes, dev)
+        _check(_lib.pointops_points_alignment(X.data_ptr(), Y.data_ptr(), _ptr(idx), _ptr(lengths), _ptr(weights), N, P,
+                                              P2, D, int(bool(estimate_scale)), int(bool(allow_reflection)), float(eps),
+                                              R.data_ptr(), T.data_ptr(), s.data_ptr(), _ptr(moments), sing.data_ptr(),
+                                              _ptr(ws), ws_bytes, _stream()),
+               "points_alignment")
+    return R, T, s, sing, moments
+
+
+def points_alignment_backward(X, Y, lengths, weights, grad_moments):
+    """grad_moments (N, 3+4D+D*D) fp64 -> grad_X, grad_Y (N,P,D) and grad_weights (N,P) (None without weights)."""
+    opt = [t for t in (lengths, weights) if t is not None]
+    dev = _require_gpu(X, Y, grad_moments, *opt)
+    X, Y = _f32c(X, "X"), _f32c(Y, "Y")
+    lengths = _i64c(lengths, "lengths") if lengths is not None else None
+    weights = _f32c(weights, "weights") if weights is not None else None
+    N, P, D = X.shape
+    if (Y.shape != X.shape or D not in POINTS_ALIGNMENT_DIMS or grad_moments.dtype != torch.float64
+            or grad_moments.shape != (N, alignment_moment_count(D))):
+        raise RuntimeError("points_alignment_backward: inconsistent shapes")
+    grad_moments = grad_moments.contiguous()
+    with _on(dev):
+        grad_X, grad_Y = torch.empty_like(X), torch.empty_like(Y)
+        grad_w = torch.empty_like(weights) if weights is not None else None
+        _check(_lib.pointops_points_alignment_backward(X.data_ptr(), Y.data_ptr(), _ptr(lengths), _ptr(weights),
+                                                       grad_moments.data_ptr(), N, P, D, grad_X.data_ptr(),
+                                                       grad_Y.data_ptr(), _ptr(grad_w), _stream()),
+               "points_alignment_backward")
+    return grad_X, grad_Y, grad_w
+
+
+class IcpState:
+    """Device buffers of one iterative_closest_point run and the stepping primitive over them.  The run OWNS its
+    search workspace -- the grid over the target cloud `Y` is built by the first step and reused by the later ones
+    (pointops_knn_points_idx_reuse) -- and never touches the grid cache above or its statistics.  `Y` and `lengths_y`
+    must not be written between steps.  History entry i lives in R[i], T[i], s[i]."""
+
+    def __init__(self, X_init, Xt, Y, lengths_x, lengths_y, max_iterations: int, estimate_scale: bool,
+                 allow_reflection: bool, relative_rmse_thr: float, reuse_grid: bool = True):
+        dev = _require_gpu(X_init, Xt, Y, lengths_x, lengths_y)
+        self.X_init, self.Y = _f32c(X_init, "X"), _f32c(Y, "Y")
+        if Xt.dtype != torch.float32 or not Xt.is_contiguous() or Xt.shape != X_init.shape \
+                or Xt.data_ptr() in (self.X_init.data_ptr(), self.Y.data_ptr()):
+            raise RuntimeError("icp: Xt must be a contiguous fp32 buffer of X's shape, distinct from X and Y")
+        self.Xt = Xt
+        self.lengths_x, self.lengths_y = _i64c(lengths_x, "lengths_x"), _i64c(lengths_y, "lengths_y")
+        N, P1, D = self.X_init.shape
+        P2 = self.Y.shape[1]
+        if (self.Y.dim() != 3 or self.Y.shape[0] != N or self.Y.shape[2] != D or D not in POINTS_ALIGNMENT_DIMS
+                or min(N, P1, P2) < 1 or self.lengths_x.shape != (N,) or self.lengths_y.shape != (N,)):
+            raise RuntimeError("icp: need X (N,P1,D), Y (N,P2,D) with N, P1, P2 >= 1, D in {2,3} and lengths (N,)")
+        self.dev, self.shape = dev, (N, P1, P2, D)
+        self.flags = (int(bool(estimate_scale)), int(bool(allow_reflection)))
+        self.thr = float(relative_rmse_thr)
+        self.steps = 0
+        self.searched = False  # the search workspace holds a grid over Y
+        with _on(dev):
+            self.R = torch.empty((max_iterations, N, D, D), dtype=torch.float32, device=dev)
+            self.T = torch.empty((max_iterations, N, D), dtype=torch.float32, device=dev)
+            self.s = torch.empty((max_iterations, N), dtype=torch.float32, device=dev)
+            self.idx = torch.empty((N, P1), dtype=torch.int64, device=dev)
+            self.dists = torch.empty((N, P1), dtype=torch.float32, device=dev)
+            self.rmse = torch.zeros((N,), dtype=torch.float32, device=dev)
+            self.converged = torch.zeros((1,), dtype=torch.int32, device=dev)
+            self.knn_ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, 1, -1)
+            self.knn_ws = _workspace(self.knn_ws_bytes, dev)
+            self.ws_bytes = _lib.pointops_icp_workspace_bytes(N, P1, D)
+            self.ws = _workspace(self.ws_bytes, dev)
+        self.uses_grid = bool(_lib.pointops_knn_uses_grid(N, P1, P2, D, 1, -1))
+        self.reuse_grid = bool(reuse_grid) and self.uses_grid
+
+    def step(self, search: bool = True) -> None:
+        """Enqueue one iteration (no synchronisation).  `search=False`: align to the neighbour table already in
+        `self.idx` (diagnostics and benchmarks)."""
+        N, P1, P2, D = self.shape
+        i = self.steps
+        if i >= self.R.shape[0]:
+            raise RuntimeError("icp: more steps than max_iterations")
+        reuse = -1 if not search else (1 if (self.reuse_grid and self.searched) else 0)
+        with _on(self.dev):
+            _check(_lib.pointops_icp_iteration(self.X_init.data_ptr(), self.Xt.data_ptr(), self.Y.data_ptr(),
+                                               self.lengths_x.data_ptr(), self.lengths_y.data_ptr(), N, P1, P2, D,
+                                               self.flags[0], self.flags[1], int(i == 0), reuse, self.thr,
+                                               self.idx.data_ptr(), self.dists.data_ptr(), self.R[i].data_ptr(),
+                                               self.T[i].data_ptr(), self.s[i].data_ptr(), self.rmse.data_ptr(),
+                                               self.converged.data_ptr(), _ptr(self.knn_ws), self.knn_ws_bytes,
+                                               _ptr(self.ws), self.ws_bytes, _stream()),
+                   "icp_iteration")
+        self.searched = self.searched or search
+        self.steps = i + 1
 
 
 # --- device halves of knn_gather / masked_gather (functions/knn.py:200-250) -------

@@ -4,8 +4,10 @@ from .. import ops as _ops  # noqa: F401  registers torch.ops.pointops_amd.* (to
 from .ball_query import ball_query
 from .knn import knn_gather, knn_points
 from .packed_to_padded import packed_to_padded, padded_to_packed
+from .points_alignment import (ICPSolution, SimilarityTransform, corresponding_points_alignment,
+                               iterative_closest_point)
 from .points_normals import estimate_pointcloud_local_coord_frames, estimate_pointcloud_normals
 from .sample_farthest_points import sample_farthest_points
-from .utils import get_point_covariances, masked_gather, wmean
+from .utils import convert_pointclouds_to_tensor, get_point_covariances, masked_gather, wmean
 
 __all__ = [k for k in globals().keys() if not k.startswith("_")]

@@ -1,0 +1,319 @@
+"""corresponding_points_alignment / iterative_closest_point -- the API of PyTorch3D's ops/points_alignment.py, the
+registration pair that sits on top of `knn_points`.
+
+Row-vector convention throughout: a transform (R, T, s) maps `X` to `s[:, None, None] * X @ R + T[:, None]`.
+
+CUDA float32 clouds of dimension 2 or 3 run on the fused HIP path (csrc/points_alignment.hip): one pass over the
+points into a few fp64 moments per cloud, one d x d solve per cloud, and -- for ICP -- one pass that applies the
+transform and measures the residual.  An ICP run owns its search workspace, so the grid over the unmodified target
+cloud is built by the first iteration only; the loop reads back 4 bytes (the "every cloud converged" word) per
+iteration.  Anything else (d > 3, float64, CPU tensors for the alignment) goes through the plain torch composition of
+the same definitions kept below.
+"""
+import warnings
+from collections import namedtuple
+from typing import List, Optional, Union
+
+import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from .. import _C
+from ..structures.pointclouds import Pointclouds
+from .knn import knn_gather, knn_points
+from .utils import convert_pointclouds_to_tensor
+
+# (R (N,d,d), T (N,d), s (N,))
+SimilarityTransform = namedtuple("SimilarityTransform", "R T s")
+ICPSolution = namedtuple("ICPSolution", "converged rmse Xt RTs t_history")
+
+AMBIGUOUS_ROT_SINGULAR_THR = 1e-15
+_ICP_EPS = 1e-9
+
+
+def _fused(*tensors) -> bool:
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors) \
+        and tensors[0].shape[2] in _C.POINTS_ALIGNMENT_DIMS
+
+
+def _capturing(t: torch.Tensor) -> bool:
+    return t.is_cuda and torch.cuda.is_current_stream_capturing()
+
+
+def _valid_mask(lengths: torch.Tensor, P: int) -> torch.Tensor:
+    return torch.arange(P, device=lengths.device)[None, :] < lengths[:, None]
+
+
+# ------------------------------------------------------------------------------------------- torch composition
+def _alignment_torch(X, Y, w, estimate_scale: bool, allow_reflection: bool, eps: float):
+    """The definition in plain torch: X, Y (N,P,d), w (N,P) already masked -> R, T, s and the singular values."""
+    N, _, d = X.shape
+    W = w.sum(1).clamp(min=eps)
+    xm = (w[..., None] * X).sum(1) / W[:, None]
+    ym = (w[..., None] * Y).sum(1) / W[:, None]
+    Xc = (X - xm[:, None]) * w[..., None]
+    Yc = (Y - ym[:, None]) * w[..., None]
+    C = torch.bmm(Xc.transpose(1, 2), Yc) / W[:, None, None]
+    U, S, Vh = torch.linalg.svd(C)
+    E = torch.ones((N, d), dtype=X.dtype, device=X.device)
+    if not allow_reflection:
+        E[:, -1] = torch.det(torch.bmm(U, Vh)).detach()
+    R = torch.bmm(U * E[:, None, :], Vh)
+    if estimate_scale:
+        xcov = (Xc * Xc).sum((1, 2)) / W
+        s = (E * S).sum(1) / xcov.clamp(min=eps)
+    else:
+        s = torch.ones((N,), dtype=X.dtype, device=X.device)
+    T = ym - s[:, None] * torch.bmm(xm[:, None, :], R)[:, 0]
+    return R, T, s, S
+
+
+def _solve_from_moments(M, px, py, d: int, estimate_scale: bool, allow_reflection: bool, eps: float):
+    """R, T, s from the kernel's raw moments M (N, 3+4d+d*d) about the pivots px, py (float64, differentiable)."""
+    N = M.shape[0]
+    Sw, Sw2 = M[:, 0], M[:, 1]
+    Swx, Swy, Sw2x, Sw2y = (M[:, 2 + k * d:2 + (k + 1) * d] for k in range(4))
+    Sxy = M[:, 2 + 4 * d:2 + 4 * d + d * d].reshape(N, d, d)
+    Sxx = M[:, 2 + 4 * d + d * d]
+    W = Sw.clamp(min=eps)
+    xm, ym = Swx / W[:, None], Swy / W[:, None]
+    C = (Sxy - xm[:, :, None] * Sw2y[:, None, :] - Sw2x[:, :, None] * ym[:, None, :]
+         + Sw2[:, None, None] * xm[:, :, None] * ym[:, None, :]) / W[:, None, None]
+    U, S, Vh = torch.linalg.svd(C)
+    E = torch.ones((N, d), dtype=M.dtype, device=M.device)
+    if not allow_reflection:
+        E[:, -1] = torch.sign(torch.det(torch.bmm(U, Vh))).detach()
+    R = torch.bmm(U * E[:, None, :], Vh)
+    if estimate_scale:
+        xcov = (Sxx - 2.0 * (xm * Sw2x).sum(1) + Sw2 * (xm * xm).sum(1)) / W
+        s = (E * S).sum(1) / xcov.clamp(min=eps)
+    else:
+        s = torch.ones((N,), dtype=M.dtype, device=M.device)
+    T = (py + ym) - s[:, None] * torch.bmm((px + xm)[:, None, :], R)[:, 0]
+    return R, T, s
+
+
+class _alignment(Function):
+    """Fused forward; backward = float64 autograd of the N tiny solves from the saved moments, then one elementwise
+    kernel that pushes the moment gradients to X, Y and the weights."""
+
+    @staticmethod
+    def forward(ctx, X, Y, lengths, weights, estimate_scale, allow_reflection, eps):
+        R, T, s, sing, moments = _C.points_alignment(X, Y, None, lengths, weights, estimate_scale, allow_reflection,
+                                                     eps, want_moments=True)
+        ctx.save_for_backward(X, Y, moments, *[t for t in (lengths, weights) if t is not None])
+        ctx.has = (lengths is not None, weights is not None)
+        ctx.flags = (estimate_scale, allow_reflection, eps)
+        ctx.mark_non_differentiable(sing)
+        return R, T, s, sing
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gR, gT, gs, _gsing):
+        X, Y, moments, *rest = ctx.saved_tensors
+        lengths = rest.pop(0) if ctx.has[0] else None
+        weights = rest.pop(0) if ctx.has[1] else None
+        N, P, d = X.shape
+        if N == 0 or P == 0:
+            return torch.zeros_like(X), torch.zeros_like(Y), None, \
+                (torch.zeros_like(weights) if weights is not None else None), None, None, None
+        # the kernel's pivots: row 0 of each cloud with at least one row (the result does not depend on them, so they
+        # are constants of the differentiation)
+        has = (lengths > 0)[:, None] if lengths is not None else torch.ones((N, 1), dtype=torch.bool, device=X.device)
+        px = torch.where(has, X[:, 0].double(), 0.0)
+        py = torch.where(has, Y[:, 0].double(), 0.0)
+        with torch.enable_grad():
+            M = moments.detach().clone().requires_grad_(True)
+            outs = _solve_from_moments(M, px, py, d, *ctx.flags)
+            wanted = [(o, g.double()) for o, g in zip(outs, (gR, gT, gs)) if o.requires_grad]
+            (gM,) = torch.autograd.grad([o for o, _ in wanted], [M], [g for _, g in wanted])
+        gX, gY, gW = _C.points_alignment_backward(X, Y, lengths, weights, gM)
+        return gX, gY, None, gW, None, None, None
+
+
+def corresponding_points_alignment(
+    X: Union[torch.Tensor, Pointclouds],
+    Y: Union[torch.Tensor, Pointclouds],
+    weights: Union[torch.Tensor, List[torch.Tensor], None] = None,
+    estimate_scale: bool = False,
+    allow_reflection: bool = False,
+    eps: float = 1e-9,
+) -> SimilarityTransform:
+    """The similarity transform (R, T, s) that minimises sum_i w_i |s x_i R + T - y_i|^2 over corresponding points
+    (weighted Umeyama / Kabsch), per cloud.
+
+    `X`, `Y`: padded (N,P,d) tensors or `Pointclouds` of equal sizes; `weights`: (N,P) tensor or a list of (P_n,)
+    tensors, default 1 for every valid point (rows past a cloud's length always weigh 0).  With W = max(sum w, eps):
+    xm = sum w x / W, ym likewise, C = sum w^2 (x - xm)(y - ym)^T / W = U S V^T, R = U E V^T with
+    E = diag(1, .., 1, det(U V^T)) (E = I with `allow_reflection`), s = tr(E S) / max(sum w^2 |x - xm|^2 / W, eps) with
+    `estimate_scale` (else 1) and T = ym - s xm R.  Returns SimilarityTransform(R (N,d,d), T (N,d), s (N,)).
+
+    A rank-deficient C (collinear or coincident points, an empty cloud) gives a finite orthogonal R on the fused path
+    (the identity for C = 0).  The two warnings (a cloud with fewer than d+1 points; an ambiguous rotation) read a flag
+    back from the device and are skipped while a stream is being captured.  Differentiable w.r.t. `X`, `Y`, `weights`.
+    """
+    Xt, num_points = convert_pointclouds_to_tensor(X)
+    Yt, num_points_Y = convert_pointclouds_to_tensor(Y)
+    containers = isinstance(X, Pointclouds) or isinstance(Y, Pointclouds)
+    if Xt.shape != Yt.shape:
+        raise ValueError("Point sets X and Y have to have the same number of batches, points and dimensions.")
+    if containers and not _capturing(num_points) and not torch.equal(num_points, num_points_Y.to(num_points.device)):
+        raise ValueError("Point sets X and Y have to have the same number of batches, points and dimensions.")
+    if weights is not None:
+        if isinstance(weights, (list, tuple)):
+            weights = torch.nn.utils.rnn.pad_sequence(list(weights), batch_first=True) if len(weights) else \
+                Xt.new_zeros(Xt.shape[:2])
+            if weights.shape[1] < Xt.shape[1]:
+                weights = torch.nn.functional.pad(weights, (0, Xt.shape[1] - weights.shape[1]))
+        if Xt.shape[:2] != weights.shape:
+            raise ValueError("weights should have the same first two dimensions as X.")
+    N, P, d = Xt.shape
+    lengths = num_points if containers else None
+
+    if _fused(Xt, Yt) and (weights is None or (weights.is_cuda and weights.dtype == torch.float32)):
+        differentiable = torch.is_grad_enabled() and (
+            Xt.requires_grad or Yt.requires_grad or (weights is not None and weights.requires_grad))
+        if differentiable:
+            R, T, s, sing = _alignment.apply(Xt, Yt, lengths, weights, bool(estimate_scale), bool(allow_reflection),
+                                             float(eps))
+        else:
+            R, T, s, sing, _ = _C.points_alignment(Xt, Yt, None, lengths, weights, estimate_scale, allow_reflection,
+                                                   eps)
+    else:
+        if Xt.is_cuda != Yt.is_cuda or Xt.dtype != Yt.dtype:
+            raise ValueError("X and Y have to be on the same device and of the same dtype.")
+        w = _valid_mask(num_points, P).to(Xt.dtype)
+        if weights is not None:
+            w = w * weights.to(Xt.dtype)
+        R, T, s, sing = _alignment_torch(Xt, Yt, w, estimate_scale, allow_reflection, eps)
+
+    if N > 0 and not _capturing(Xt) and not torch.compiler.is_compiling():
+        few = (num_points < d + 1).any() if containers else torch.tensor(P < d + 1, device=sing.device)
+        few, ambiguous = torch.stack((few.to(sing.device), (sing.detach() <= AMBIGUOUS_ROT_SINGULAR_THR).any())).tolist()
+        if few:
+            warnings.warn("The size of one of the point clouds is <= dim+1. corresponding_points_alignment cannot "
+                          "return a unique rotation.")
+        if ambiguous:
+            warnings.warn("Excessively low rank of cross-correlation between aligned point clouds. "
+                          "corresponding_points_alignment cannot return a unique rotation.")
+    return SimilarityTransform(R, T, s)
+
+
+# --------------------------------------------------------------------------------------------------------- ICP
+def _apply_transform(X, RTs, mask):
+    R, T, s = RTs
+    return (s[:, None, None] * torch.bmm(X, R) + T[:, None, :]) * mask[..., None].to(X.dtype)
+
+
+def _check_init_transform(init_transform, N: int, d: int, like: torch.Tensor):
+    try:
+        R, T, s = init_transform
+    except Exception:
+        raise ValueError("The initial transformation init_transform has to be a named tuple SimilarityTransform "
+                         "with elements (R, T, s).") from None
+    if not all(torch.is_tensor(t) for t in (R, T, s)) or R.shape != (N, d, d) or T.shape != (N, d) or s.shape != (N,):
+        raise ValueError("The initial transformation init_transform has to be a named tuple SimilarityTransform with "
+                         "elements (R, T, s). R are dim x dim orthonormal matrices of shape (minibatch, dim, dim), T "
+                         "is a batch of dim-dimensional translations of shape (minibatch, dim) and s is a batch of "
+                         "scalars of shape (minibatch,).")
+    return SimilarityTransform(*(t.detach().to(device=like.device, dtype=like.dtype) for t in (R, T, s)))
+
+
+def _report(iteration: int, rmse: torch.Tensor, prev: Optional[torch.Tensor]) -> None:
+    rel = torch.ones_like(rmse) if prev is None else torch.where(prev > 0, (prev - rmse) / prev, torch.zeros_like(rmse))
+    print("ICP iteration %d: mean/max rmse = %1.2e/%1.2e ; mean relative rmse = %1.2e"
+          % (iteration, float(rmse.mean()), float(rmse.max()), float(rel.mean())))
+
+
+def _icp_torch(X_init, Xt, Yt, num_points_X, num_points_Y, max_iterations, relative_rmse_thr, estimate_scale,
+               allow_reflection, verbose):
+    """The iteration in plain torch over the public knn_points / knn_gather (what a user composes from the package's
+    search): the route of every shape the fused path does not cover."""
+    mask = _valid_mask(num_points_X, X_init.shape[1])
+    w = mask.to(X_init.dtype)
+    prev, history, converged = None, [], False
+    for iteration in range(max_iterations):
+        idx = knn_points(Xt.float(), Yt.float(), lengths1=num_points_X, lengths2=num_points_Y, K=1).idx
+        Y_nn = knn_gather(Yt, idx, num_points_Y)[:, :, 0]
+        R, T, s, _ = _alignment_torch(X_init, Y_nn, w, estimate_scale, allow_reflection, _ICP_EPS)
+        history.append(SimilarityTransform(R, T, s))
+        Xt = _apply_transform(X_init, history[-1], mask)
+        rmse = ((((Xt - Y_nn) ** 2).sum(2) * w).sum(1) / num_points_X.to(w.dtype).clamp(min=_ICP_EPS)).sqrt()
+        rel = torch.ones_like(rmse) if prev is None else \
+            torch.where(prev > 0, (prev - rmse) / prev, torch.zeros_like(rmse))
+        if verbose:
+            _report(iteration, rmse, prev)
+        prev = rmse
+        if bool((rel <= relative_rmse_thr).all()):
+            converged = True
+            break
+    return converged, prev, Xt, history
+
+
+def iterative_closest_point(
+    X: Union[torch.Tensor, Pointclouds],
+    Y: Union[torch.Tensor, Pointclouds],
+    init_transform: Optional[SimilarityTransform] = None,
+    max_iterations: int = 100,
+    relative_rmse_thr: float = 1e-6,
+    estimate_scale: bool = False,
+    allow_reflection: bool = False,
+    verbose: bool = False,
+    *,
+    _reuse_grid: bool = True,
+) -> ICPSolution:
+    """Point-to-point ICP of every cloud of `X` (N,P1,d) onto the cloud of `Y` (N,P2,d) with the same batch index.
+
+    Starting from Xt = X (or `init_transform` applied to X), iteration i finds the nearest neighbour in `Y` of every
+    valid row of Xt (`knn_points`, K = 1, L2, lengths honoured), aligns the ORIGINAL X to those neighbours
+    (`corresponding_points_alignment` with the validity mask as weights), sets Xt = s X R + T and
+    rmse[n] = sqrt(sum_valid |Xt - Y[nn]|^2 / max(len_X[n], 1e-9)).  It stops with `converged = True` once the relative
+    change (prev - rmse) / prev is <= `relative_rmse_thr` for every cloud; the change counts as 1 on the first
+    iteration and as 0 for a cloud whose previous rmse is 0 (an empty or exactly matched cloud cannot block the others).
+
+    Returns ICPSolution(converged, rmse (N,), Xt (a `Pointclouds` when `X` is one, else (N,P1,d); padded rows zero),
+    RTs = the last transform, t_history = the transform of every iteration).
+
+    NOT differentiable: the loop runs under `torch.no_grad()` and every returned tensor is detached.  `Y` must not be
+    written while the call runs (the fused path builds its search grid over `Y` once).  `_reuse_grid=False` rebuilds
+    the grid in every iteration; results are bit-identical either way.
+    """
+    Xt, num_points_X = convert_pointclouds_to_tensor(X)
+    Yt, num_points_Y = convert_pointclouds_to_tensor(Y)
+    if Xt.shape[0] != Yt.shape[0] or Xt.shape[2] != Yt.shape[2]:
+        raise ValueError("Point sets X and Y have to have the same batch size and dimensionality.")
+    if Xt.device != Yt.device or Xt.dtype != Yt.dtype:
+        raise ValueError("X and Y have to be on the same device and of the same dtype.")
+    max_iterations = int(max_iterations)
+    if max_iterations < 1:
+        raise ValueError("max_iterations has to be >= 1.")
+    N, P1, d = Xt.shape
+    if init_transform is not None:
+        init_transform = _check_init_transform(init_transform, N, d, Xt)
+
+    with torch.no_grad():
+        X_init = Xt.detach().contiguous()
+        Yt = Yt.detach().contiguous()
+        mask = _valid_mask(num_points_X, P1)
+        cur = X_init.clone() if init_transform is None else _apply_transform(X_init, init_transform, mask).contiguous()
+        if _fused(X_init, Yt) and min(N, P1, Yt.shape[1]) >= 1:
+            state = _C.IcpState(X_init, cur, Yt, num_points_X, num_points_Y, max_iterations, estimate_scale,
+                                allow_reflection, relative_rmse_thr, reuse_grid=_reuse_grid)
+            converged, prev = False, None
+            for iteration in range(max_iterations):
+                state.step()
+                if verbose:
+                    rmse = state.rmse.clone()
+                    _report(iteration, rmse, prev)
+                    prev = rmse
+                if int(state.converged.item()):  # the loop's only device-to-host read: 4 bytes
+                    converged = True
+                    break
+            history = [SimilarityTransform(state.R[i], state.T[i], state.s[i]) for i in range(state.steps)]
+            rmse, Xt_out = state.rmse, state.Xt
+        else:
+            converged, rmse, Xt_out, history = _icp_torch(X_init, cur, Yt, num_points_X, num_points_Y, max_iterations,
+                                                          relative_rmse_thr, estimate_scale, allow_reflection, verbose)
+    if isinstance(X, Pointclouds):
+        Xt_out = X.update_padded(Xt_out)
+    return ICPSolution(converged, rmse, Xt_out, history[-1], history)

@@ -63,6 +63,20 @@ def wmean(
     return (x * weight[..., None]).sum(**args) / weight[..., None].sum(**args).clamp(eps)
 
 
+def convert_pointclouds_to_tensor(pcl) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(padded points (N,P,D), lengths (N,) int64) of a `Pointclouds` or of a padded tensor (every cloud of length P)
+    -- the helper of PyTorch3D's ops/utils.py that its points_alignment functions start from."""
+    from ..structures.pointclouds import Pointclouds
+
+    if isinstance(pcl, Pointclouds):
+        return pcl.points_padded(), pcl.num_points_per_cloud()
+    if torch.is_tensor(pcl):
+        if pcl.dim() != 3:
+            raise ValueError("The inputs have to be Pointclouds objects or padded tensors of shape (minibatch, P, dim).")
+        return pcl, torch.full((pcl.shape[0],), pcl.shape[1], dtype=torch.int64, device=pcl.device)
+    raise ValueError("The inputs X, Y should be either Pointclouds objects or tensors.")
+
+
 def get_point_covariances(
     points_padded: torch.Tensor,
     num_points_per_cloud: torch.Tensor,
