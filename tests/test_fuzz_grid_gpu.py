@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import frames
+
 pytestmark = pytest.mark.gpu
 
 _SOAK = int(os.environ.get("POINTOPS_FUZZ_SOAK", "0"))
@@ -121,3 +123,66 @@ def test_fuzz_ball_query_grid_vs_scan(dev, monkeypatch, seed):
             got_i, got_d = _C.ball_query(ta, tb, t1, t2, K, radius)
             assert torch.equal(got_i, want_i), dict(what, knob=knob)
             assert torch.equal(got_d.view(torch.int32), want_d.view(torch.int32)), dict(what, knob=knob)
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_fuzz_grid_family_in_coordinate_frames(dev, monkeypatch, seed):
+    """The same distributions in a random coordinate frame per iteration (tests/frames.py: exact shifts, negations and
+    2^k scalings of the base quantised to 2^-20; offsets, per-axis scales, magnitudes 1e18 / 1e-18, a constant negative
+    axis, clouds of opposite sign, a far outlier): version 3 with the quad pass on and off, and the ball query's grid,
+    against version 0 / `ball_grid=0` on the TRANSFORMED inputs, bit for bit; in an exact frame also against the
+    untransformed call (same idx, dists times the exact factor)."""
+    from pytorch3d_pointops_amd import _C
+
+    rng = np.random.default_rng(990 + seed + _SOAK)
+    kinds = ["uniform", "clusters", "lattice", "slab", "u4"]
+    for it in range(10):
+        d = int(rng.choice([1, 2, 3, 3, 3]))
+        n = int(rng.integers(1, 4))
+        p1, p2 = int(rng.integers(500, 20000)), int(rng.integers(500, 30000))
+        K = int(rng.choice([1, 4, 8, 16, 32, 40, 64, 100]))
+        norm = int(rng.integers(1, 3))
+        k1, k2 = kinds[int(rng.integers(0, 5))], kinds[int(rng.integers(0, 5))]
+        lattice = k1 == "lattice" and k2 == "lattice"
+        a, b = _draw(rng, n, p1, d, k1), _draw(rng, n, p2, d, k2)
+        if not lattice:
+            a, b = frames.quantise(a, 20), frames.quantise(b, 20)
+        pool = frames.frames_for(lattice=lattice)
+        frame = pool[int(rng.integers(0, len(pool)))]
+        fa, fb = frame.apply(a, b)
+        l1 = rng.integers(1, p1 + 1, n).astype(np.int64)
+        l2 = rng.integers(1, p2 + 1, n).astype(np.int64)
+        l1[int(rng.integers(0, n))] = p1
+        l2[int(rng.integers(0, n))] = p2
+        t1, t2 = torch.from_numpy(l1).to(dev), torch.from_numpy(l2).to(dev)
+        ta, tb = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+        tfa, tfb = torch.from_numpy(fa).to(dev), torch.from_numpy(fb).to(dev)
+        what = dict(seed=seed, it=it, frame=frame.name, d=d, n=n, p1=p1, p2=p2, K=K, norm=norm, k1=k1, k2=k2,
+                    l1=l1.tolist(), l2=l2.tolist())
+        monkeypatch.delenv("POINTOPS_DEBUG", raising=False)
+        want_i, want_d = _C.knn_points_idx(tfa, tfb, t1, t2, norm, K, 0)
+        if frame.exact:
+            base_i, base_d = _C.knn_points_idx(ta, tb, t1, t2, norm, K, 0)
+            assert torch.equal(want_i, base_i), dict(what, against="untransformed")
+            assert torch.equal(want_d.view(torch.int32), (base_d * float(frame.dist_factor(norm))).view(torch.int32)), \
+                dict(what, against="untransformed")
+        for knob in ("grid_quad=1", "grid_quad=0"):
+            monkeypatch.setenv("POINTOPS_DEBUG", knob)
+            got_i, got_d = _C.knn_points_idx(tfa, tfb, t1, t2, norm, K, 3)
+            assert torch.equal(got_i, want_i), dict(what, knob=knob)
+            assert torch.equal(got_d.view(torch.int32), want_d.view(torch.int32)), dict(what, knob=knob)
+        # ball query: a radius of a few point spacings of the base, carried into the frame
+        BK = int(rng.choice([4, 8, 16, 33]))
+        radius = float(np.float32(10.0 ** rng.uniform(-2.5, -0.5)))
+        fr = frame.radius(radius) if frame.exact else radius * frame.rscale
+        monkeypatch.setenv("POINTOPS_DEBUG", "ball_grid=0")
+        want_i, want_d = _C.ball_query(tfa, tfb, t1, t2, BK, fr)
+        if frame.exact:
+            base_i, base_d = _C.ball_query(ta, tb, t1, t2, BK, radius)
+            assert torch.equal(want_i, base_i), dict(what, BK=BK, radius=radius, against="untransformed")
+            assert torch.equal(want_d.view(torch.int32), (base_d * float(frame.dist_factor(2))).view(torch.int32)), \
+                dict(what, BK=BK, radius=radius, against="untransformed")
+        monkeypatch.setenv("POINTOPS_DEBUG", "ball_grid=1")
+        got_i, got_d = _C.ball_query(tfa, tfb, t1, t2, BK, fr)
+        assert torch.equal(got_i, want_i), dict(what, BK=BK, radius=radius)
+        assert torch.equal(got_d.view(torch.int32), want_d.view(torch.int32)), dict(what, BK=BK, radius=radius)
