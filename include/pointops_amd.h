@@ -260,9 +260,11 @@ int pointops_chamfer_backward_accumulate(const float* x, const float* y, const i
  *   idx_xy (N,P1), idx_yx (N,P2): the neighbour indices, outputs, needed by the backward.
  * The backward takes 1+F gradient pointers (HOST array; a null entry is a zero gradient; each points to one float
  * after a batch reduction, to N floats without one) and writes grad_x, grad_y, grad_x_feats, grad_y_feats
- * (every element written: no pre-zeroing needed); workspace: (1+F)*N floats.
+ * (every element written: no pre-zeroing needed); workspace: pointops_chamfer_pair_backward_workspace_bytes(N, F), the
+ * (1+F)*N floats of the per-cloud output gradients.
  */
 size_t pointops_chamfer_pair_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D, int F);
+size_t pointops_chamfer_pair_backward_workspace_bytes(int64_t N, int F);
 int pointops_chamfer_pair_forward(const float* x, const float* y, const int64_t* x_lengths,
                                   const int64_t* y_lengths, int64_t N, int64_t P1, int64_t P2, int64_t D, int norm,
                                   int F, const float* const* x_feats, const float* const* y_feats, const int64_t* C,

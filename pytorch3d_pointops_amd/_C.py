@@ -9,8 +9,11 @@ functions: CPU tensors raise ``RuntimeError`` (the mirror image of the reference
 "Not compiled with GPU support." -- csrc/knn/knn.h:74), and a missing shared
 library raises at import of this module.
 """
+import collections
 import ctypes
 import os
+import types
+import weakref
 
 import torch  # must be imported first: loads the process-wide HIP runtime (libamdhip64.so.7)
 
@@ -25,7 +28,8 @@ _f32 = ctypes.c_float
 _f64 = ctypes.c_double
 _sz = ctypes.c_size_t
 
-# name -> (restype, argtypes); must list every symbol of include/pointops_amd.h
+# name -> (restype, argtypes): every prototype of include/pointops_amd.h, type by type (tests/test_boundary_cpu.py
+# parses the header and compares)
 _SIGNATURES = {
     "pointops_abi_version": (_int, []),
     "pointops_target_arch": (ctypes.c_char_p, []),
@@ -77,6 +81,7 @@ _SIGNATURES = {
     "pointops_chamfer_backward_accumulate": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
                                                     _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "pointops_chamfer_pair_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
+    "pointops_chamfer_pair_backward_workspace_bytes": (_sz, [_i64, _int]),
     "pointops_chamfer_pair_forward": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp,
                                              _int, _int, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pointops_chamfer_pair_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int,
@@ -112,9 +117,15 @@ def _check(code, what):
         raise RuntimeError(f"{what} failed ({code}): {_lib.pointops_last_error().decode()}")
 
 
+# ---------------------------------------------------------------------------
+# Argument normalisers.  None (an optional tensor) passes through all of them.
+# ---------------------------------------------------------------------------
 def _require_gpu(*tensors):
+    """The one device of the tensors; this check comes first in every wrapper."""
     dev = None
     for t in tensors:
+        if t is None:
+            continue
         if not t.is_cuda:
             raise RuntimeError(
                 "pytorch3d_pointops_amd is a GPU-only (MI355X / gfx950) implementation: got a CPU "
@@ -128,23 +139,35 @@ def _require_gpu(*tensors):
 
 
 def _contig(t, name):
+    """`t` itself, which must be contiguous already: where the reference raises (CHECK_CONTIGUOUS) or the call writes
+    into the caller's tensor, a silent copy would be wrong."""
     if not t.is_contiguous():
         raise RuntimeError(f"{name} must be contiguous")
+    return t
 
 
-def _f32c(t, name):
-    """fp32 + contiguous view of a device tensor whose data pointer goes to a kernel."""
+def _f32c(t, name, copy=True):
+    """fp32 + contiguous view of a device tensor whose data pointer goes to a kernel (`copy=False`: see _contig)."""
+    if t is None:
+        return None
     if t.dtype != torch.float32:
-        raise RuntimeError(f"expected scalar type Float for {name}")
-    return t.contiguous()
+        raise RuntimeError(f"expected scalar type Float for {name}")  # CPU ref: same restriction
+    return t.contiguous() if copy else _contig(t, name)
 
 
 def _i64c(t, name):
+    """The kernels read int64 through raw pointers: any other integer type would be read past its buffer (the
+    reference's accessor<int64_t, 1> raises: knn_cpu.cpp:84-88)."""
+    if t is None:
+        return None
     if t.dtype != torch.int64:
         raise RuntimeError(f"{name} must be int64")
     return t.contiguous()
 
 
+# ---------------------------------------------------------------------------
+# The native call: device guard, current stream, pointers, error check.
+# ---------------------------------------------------------------------------
 class _NoGuard:
     def __enter__(self):
         return None
@@ -158,8 +181,9 @@ _NO_GUARD = _NoGuard()
 
 def _on(dev):
     """Device guard for the launches: torch.cuda.device(dev) only when `dev` is not already current (its constructor,
-    __enter__ and __exit__ cost ~4 us of a small call; the usual single-GPU process never needs the switch)."""
-    return _NO_GUARD if dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
+    __enter__ and __exit__ cost ~4 us of a small call; the usual single-GPU process never needs the switch).  None: the
+    caller holds the guard already."""
+    return _NO_GUARD if dev is None or dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -172,6 +196,26 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _bind(name, argtypes):
+    """Python caller `f(what, dev, *args)` of one stream-taking entry: under the guard of `dev`, with every pointer
+    argument's data_ptr() (None: a null pointer; a bool goes as an int by itself) and the current stream appended,
+    raising through _check under the display name `what`.  It is compiled once from the entry's argtypes because these
+    calls are host-bound at small sizes: converting in a loop with a type test per argument costs 1-2 us of a 13 us
+    knn_points call (tools/host_overhead.py), this costs what the hand-written call did."""
+    names = [f"a{i}" for i in range(len(argtypes) - 1)]  # (the last argument is the stream)
+    conv = [f"{n}.data_ptr() if {n} is not None else None" if t is _vp else n for n, t in zip(names, argtypes)]
+    scope = {}
+    exec(f"def {name}(what, dev, {', '.join(names)}):\n"
+         f"    with _on(dev):\n"
+         f"        _check(_lib.{name}({', '.join(conv)}, _stream()), what)\n", globals(), scope)
+    return scope[name]
+
+
+# _call.<entry without "pointops_">(what, dev, *args) for every entry that launches (returns a code, takes a stream)
+_call = types.SimpleNamespace(**{name[len("pointops_"):]: _bind(name, args) for name, (res, args) in _SIGNATURES.items()
+                                 if res is _int and args and args[-1] is _vp})
+
+
 def _workspace(nbytes: int, dev):
     """Device scratch of one native call, or None when it needs none.  A fresh tensor per call: the caching allocator
     is stream-ordered (the block is handed out again only behind this call's launches), and inside a HIP-graph capture
@@ -179,8 +223,11 @@ def _workspace(nbytes: int, dev):
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
+def _scratch(dev, sizer, *dims):
+    """(workspace, workspace_bytes) of one native call, sized by the library's own `sizer(*dims)`: the adjacent pair
+    of arguments every entry with scratch takes."""
+    nbytes = sizer(*dims)
+    return _workspace(nbytes, dev), nbytes
 
 
 # ---------------------------------------------------------------------------
@@ -195,9 +242,6 @@ def _ptr(t):
 # has no such failure mode).
 #   pytorch3d_pointops_amd.set_grid_cache(True [, max_entries])      or      POINTOPS_GRID_CACHE=1
 # ---------------------------------------------------------------------------
-import collections
-import weakref
-
 _GRID_CACHE = collections.OrderedDict()
 _GRID_CACHE_ON = os.environ.get("POINTOPS_GRID_CACHE", "0") not in ("", "0")
 _GRID_CACHE_MAX = 2
@@ -216,6 +260,10 @@ def set_grid_cache(enabled: bool, max_entries: int = 2) -> None:
     _GRID_CACHE_MAX = max(1, int(max_entries))
     if not enabled:
         _GRID_CACHE.clear()
+
+
+def grid_cache_enabled() -> bool:
+    return _GRID_CACHE_ON
 
 
 def _sig(t):
@@ -250,33 +298,27 @@ def _grid_workspace(p1, p2, lengths1, lengths2, shape, ws_bytes, dev):
 # ---------------------------------------------------------------------------
 def knn_points_idx(p1, p2, lengths1, lengths2, norm: int, K: int, version: int = -1):
     dev = _require_gpu(p1, p2, lengths1, lengths2)
-    if p1.dtype != torch.float32 or p2.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for p1/p2")  # CPU ref: same restriction
-    if lengths1.dtype != torch.int64 or lengths2.dtype != torch.int64:
-        raise RuntimeError("lengths1/lengths2 must be int64")
-    p1, p2 = p1.contiguous(), p2.contiguous()  # reference CUDA path: knn.cu:373-376
-    lengths1, lengths2 = lengths1.contiguous(), lengths2.contiguous()
-    # (a self-query -- the same storage for both point sets and both lengths -- is recognised by the C ABI
-    # from pointer equality and sorts the cloud once)
+    # (a self-query -- the same storage for both point sets and both lengths -- is recognised by the C ABI from pointer
+    # equality and sorts the cloud once: .contiguous() of a contiguous tensor is the tensor itself)
+    p1, p2 = _f32c(p1, "p1"), _f32c(p2, "p2")  # reference CUDA path: knn.cu:373-376
+    lengths1, lengths2 = _i64c(lengths1, "lengths1"), _i64c(lengths2, "lengths2")
     N, P1, D = p1.shape
     P2 = p2.shape[1]
     if p2.shape[0] != N or p2.shape[2] != D or lengths1.shape != (N,) or lengths2.shape != (N,):
         raise RuntimeError("knn_points_idx: inconsistent shapes")
-    with _on(dev):
-        idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
-        ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, K, version)
-        if _GRID_CACHE_ON and ws_bytes and _lib.pointops_knn_uses_grid(N, P1, P2, D, int(K), int(version)) \
+    K, version = int(K), int(version)
+    idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, K, version)
+    with _on(dev):  # (the cache keys on the current stream of `dev`)
+        if _GRID_CACHE_ON and ws_bytes and _lib.pointops_knn_uses_grid(N, P1, P2, D, K, version) \
                 and not torch.cuda.is_current_stream_capturing():  # (a captured call must not bake a reuse level in)
-            ws, reuse, key = _grid_workspace(p1, p2, lengths1, lengths2, (N, P1, P2, D, int(K), int(version)),
-                                             ws_bytes, dev)
+            ws, reuse, key = _grid_workspace(p1, p2, lengths1, lengths2, (N, P1, P2, D, K, version), ws_bytes, dev)
         else:
             ws, reuse, key = _workspace(ws_bytes, dev), 0, None
         try:
-            _check(_lib.pointops_knn_points_idx_reuse(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
-                                                      lengths2.data_ptr(), N, P1, P2, D, int(norm), int(K),
-                                                      int(version), idxs.data_ptr(), dists.data_ptr(), _ptr(ws),
-                                                      ws_bytes, reuse, _stream()), "knn_points_idx")
+            _call.knn_points_idx_reuse("knn_points_idx", None, p1, p2, lengths1, lengths2, N, P1, P2, D, int(norm), K,
+                                       version, idxs, dists, ws, ws_bytes, reuse)
         except Exception:
             _GRID_CACHE.pop(key, None)  # a failed call may have left the grid half built
             raise
@@ -290,19 +332,17 @@ def _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, out_shape, read, what
     p2 = p1 if p2 is p1 else p2.contiguous()
     N, P1, D = p1.shape
     P2 = p2.shape[1]
+    K = int(K)
     if not knn_check_version(3, D, K):
         raise RuntimeError("grid family needs D <= 3 and K <= 128")
-    with _on(dev):
-        idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
-        ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, K, 3)
-        ws = _workspace(ws_bytes, dev)
-        out = torch.zeros(out_shape(N), dtype=torch.int32, device=dev)
-        _check(_lib.pointops_knn_points_idx(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
-                                            lengths2.data_ptr(), N, P1, P2, D, int(norm), int(K), 3,
-                                            idxs.data_ptr(), dists.data_ptr(), _ptr(ws), ws_bytes,
-                                            _stream()), "knn_points_idx")
-        _check(read(_ptr(ws), N, P1, P2, int(K), out.data_ptr(), _stream()), what)
+    idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    out = torch.zeros(out_shape(N), dtype=torch.int32, device=dev)
+    ws, ws_bytes = _scratch(dev, _lib.pointops_knn_workspace_bytes, N, P1, P2, D, K, 3)
+    with _on(dev):  # (both calls on one stream)
+        _call.knn_points_idx("knn_points_idx", None, p1, p2, lengths1, lengths2, N, P1, P2, D, int(norm), K, 3, idxs,
+                             dists, ws, ws_bytes)
+        read(what, None, ws, N, P1, P2, K, out)
     return idxs, dists, out
 
 
@@ -311,7 +351,7 @@ def knn_grid_fallback_counts(p1, p2, lengths1, lengths2, norm: int, K: int):
     counts[0, n] = queries of cloud n re-searched wave-per-query on a growing cell cube,
     counts[1, n] = queries that ended in the whole-cloud scan."""
     return _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, lambda N: (2, N),
-                             _lib.pointops_knn_grid_fallback_counts, "knn_grid_fallback_counts")
+                             _call.knn_grid_fallback_counts, "knn_grid_fallback_counts")
 
 
 def knn_grid_stats(p1, p2, lengths1, lengths2, norm: int, K: int):
@@ -319,7 +359,7 @@ def knn_grid_stats(p1, p2, lengths1, lengths2, norm: int, K: int):
     cell count, grid used, queries uncertified after the lane pass / the quad + box passes / sent to the whole-cloud
     scan, queries deferred to the box search, refined cells, bins of the point / query sort, crowded bins of the
     point / query sort."""
-    return _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, lambda N: (N, 14), _lib.pointops_knn_grid_stats,
+    return _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, lambda N: (N, 14), _call.knn_grid_stats,
                              "knn_grid_stats")
 
 
@@ -333,13 +373,8 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm: int, grad_dists,
     """`deterministic`: grad_p2 through the inverted neighbour table (csrc/backward_det.hip) -- reproducible and
     bit-equal to the reference's CPU kernel -- instead of fp32 scatter-adds (LDS tiles / device atomics)."""
     dev = _require_gpu(p1, p2, lengths1, lengths2, idxs, grad_dists)
-    if p1.dtype != torch.float32 or p2.dtype != torch.float32 or grad_dists.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float")
-    p1, p2 = p1.contiguous(), p2.contiguous()
-    # the kernels read int64 through raw pointers: any other integer type would be read past its buffer (the
-    # reference's accessor<int64_t, 1> raises: knn_cpu.cpp:84-88)
-    lengths1, lengths2 = _i64c(lengths1, "lengths1"), _i64c(lengths2, "lengths2")
-    idxs, grad_dists = _i64c(idxs, "idxs"), grad_dists.contiguous()
+    p1, p2, grad_dists = _f32c(p1, "p1"), _f32c(p2, "p2"), _f32c(grad_dists, "grad_dists")
+    lengths1, lengths2, idxs = _i64c(lengths1, "lengths1"), _i64c(lengths2, "lengths2"), _i64c(idxs, "idxs")
     if p1.dim() != 3 or p2.dim() != 3 or idxs.dim() != 3:
         raise RuntimeError("knn_points_backward: p1, p2 and idxs must be 3-dimensional")
     N, P1, D = p1.shape
@@ -348,37 +383,23 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm: int, grad_dists,
     if (p2.shape[0] != N or p2.shape[2] != D or idxs.shape != (N, P1, K) or grad_dists.shape != (N, P1, K)
             or lengths1.shape != (N,) or lengths2.shape != (N,)):
         raise RuntimeError("knn_points_backward: inconsistent shapes")
-    with _on(dev):
-        grad_p1 = torch.empty((N, P1, D), dtype=torch.float32, device=dev)
-        grad_p2 = torch.empty((N, P2, D), dtype=torch.float32, device=dev)
-        if deterministic:
-            ws_bytes = _lib.pointops_backward_det_workspace_bytes(N, P1, K, P2)
-            ws = _workspace(ws_bytes, dev)
-            _check(
-                _lib.pointops_knn_points_backward_det(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
-                                                      lengths2.data_ptr(), idxs.data_ptr(), grad_dists.data_ptr(),
-                                                      N, P1, P2, D, K, int(norm), grad_p1.data_ptr(),
-                                                      grad_p2.data_ptr(), _ptr(ws), ws_bytes, _stream()),
-                "knn_points_backward(deterministic)",
-            )
-            return grad_p1, grad_p2
-        _check(
-            _lib.pointops_knn_points_backward(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
-                                              lengths2.data_ptr(), idxs.data_ptr(),
-                                              grad_dists.data_ptr(), N, P1, P2, D, K, int(norm),
-                                              grad_p1.data_ptr(), grad_p2.data_ptr(), _stream()),
-            "knn_points_backward",
-        )
+    grad_p1 = torch.empty((N, P1, D), dtype=torch.float32, device=dev)
+    grad_p2 = torch.empty((N, P2, D), dtype=torch.float32, device=dev)
+    if deterministic:
+        entry, what = _call.knn_points_backward_det, "knn_points_backward(deterministic)"
+        scratch = _scratch(dev, _lib.pointops_backward_det_workspace_bytes, N, P1, K, P2)
+    else:
+        entry, what, scratch = _call.knn_points_backward, "knn_points_backward", ()
+    entry(what, dev, p1, p2, lengths1, lengths2, idxs, grad_dists, N, P1, P2, D, K, int(norm), grad_p1, grad_p2,
+          *scratch)
     return grad_p1, grad_p2
 
 
 # reference: csrc/ball_query/ball_query.h:62-93 -- returns (idx, dists)
 def ball_query(p1, p2, lengths1, lengths2, K: int, radius: float):
     dev = _require_gpu(p1, p2, lengths1, lengths2)
-    if p1.dtype != torch.float32 or p2.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for p1/p2")
-    p1, p2 = p1.contiguous(), p2.contiguous()  # ball_query.h:74-77
-    lengths1, lengths2 = _i64c(lengths1, "lengths1"), _i64c(lengths2, "lengths2")  # (accessor<int64_t, 1> in the reference)
+    p1, p2 = _f32c(p1, "p1"), _f32c(p2, "p2")  # ball_query.h:74-77
+    lengths1, lengths2 = _i64c(lengths1, "lengths1"), _i64c(lengths2, "lengths2")
     if p1.dim() != 3 or p2.dim() != 3:
         raise RuntimeError("ball_query: p1 and p2 must be 3-dimensional")
     N, P1, D = p1.shape
@@ -388,27 +409,17 @@ def ball_query(p1, p2, lengths1, lengths2, K: int, radius: float):
     K = int(K)
     if K < 0:
         raise RuntimeError("ball_query: K must be non-negative")
-    with _on(dev):
-        idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
-        ws_bytes = _lib.pointops_ball_query_workspace_bytes(N, P1, P2, D, int(K))
-        ws = _workspace(ws_bytes, dev)
-        _check(
-            _lib.pointops_ball_query(p1.data_ptr(), p2.data_ptr(), lengths1.data_ptr(),
-                                     lengths2.data_ptr(), N, P1, P2, D, int(K), float(radius),
-                                     idxs.data_ptr(), dists.data_ptr(), _ptr(ws), ws_bytes, _stream()),
-            "ball_query",
-        )
+    idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    _call.ball_query("ball_query", dev, p1, p2, lengths1, lengths2, N, P1, P2, D, K, float(radius), idxs, dists,
+                     *_scratch(dev, _lib.pointops_ball_query_workspace_bytes, N, P1, P2, D, K))
     return idxs, dists
 
 
 # reference: csrc/sample_farthest_points/sample_farthest_points.h:55-76
 def sample_farthest_points(points, lengths, K, start_idxs, max_K=None):
     dev = _require_gpu(points, lengths, K, start_idxs)
-    if points.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float for points")
-    points = points.contiguous()
-    # int64 through raw pointers (the reference's accessor<int64_t, 1>: sample_farthest_points_cpu.cpp:33-36)
+    points = _f32c(points, "points")
     lengths, K, start_idxs = _i64c(lengths, "lengths"), _i64c(K, "K"), _i64c(start_idxs, "start_idxs")
     if points.dim() != 3:
         raise RuntimeError("sample_farthest_points: points must be 3-dimensional")
@@ -420,16 +431,9 @@ def sample_farthest_points(points, lengths, K, start_idxs, max_K=None):
     if max_K is None:
         max_K = int(K.max().item()) if N > 0 else 0
     max_K = int(max_K) if N > 0 else 0
-    with _on(dev):
-        idxs = torch.empty((N, max_K), dtype=torch.int64, device=dev)
-        ws_bytes = _lib.pointops_fps_workspace_bytes(N, P, max_K)
-        ws = _workspace(ws_bytes, dev)
-        _check(
-            _lib.pointops_sample_farthest_points(points.data_ptr(), lengths.data_ptr(), K.data_ptr(),
-                                                 start_idxs.data_ptr(), N, P, D, max_K,
-                                                 idxs.data_ptr(), _ptr(ws), ws_bytes, _stream()),
-            "sample_farthest_points",
-        )
+    idxs = torch.empty((N, max_K), dtype=torch.int64, device=dev)
+    _call.sample_farthest_points("sample_farthest_points", dev, points, lengths, K, start_idxs, N, P, D, max_K, idxs,
+                                 *_scratch(dev, _lib.pointops_fps_workspace_bytes, N, P, max_K))
     return idxs
 
 
@@ -442,13 +446,8 @@ def packed_to_padded(inputs_packed, first_idxs, max_size: int):
     _contig(first_idxs, "first_idxs")
     F, D = inputs_packed.shape
     B = first_idxs.shape[0]
-    with _on(dev):
-        out = torch.empty((B, max_size, D), dtype=torch.float32, device=dev)
-        _check(
-            _lib.pointops_packed_to_padded(inputs_packed.data_ptr(), first_idxs.data_ptr(), F, B,
-                                           int(max_size), D, out.data_ptr(), _stream()),
-            "packed_to_padded",
-        )
+    out = torch.empty((B, max_size, D), dtype=torch.float32, device=dev)
+    _call.packed_to_padded("packed_to_padded", dev, inputs_packed, first_idxs, F, B, int(max_size), D, out)
     return out
 
 
@@ -460,33 +459,20 @@ def padded_to_packed(inputs_padded, first_idxs, num_inputs: int):
     _contig(inputs_padded, "inputs_padded")
     _contig(first_idxs, "first_idxs")
     B, M, D = inputs_padded.shape
-    with _on(dev):
-        out = torch.empty((int(num_inputs), D), dtype=torch.float32, device=dev)
-        _check(
-            _lib.pointops_padded_to_packed(inputs_padded.data_ptr(), first_idxs.data_ptr(),
-                                           int(num_inputs), B, M, D, out.data_ptr(), _stream()),
-            "padded_to_packed",
-        )
+    out = torch.empty((int(num_inputs), D), dtype=torch.float32, device=dev)
+    _call.padded_to_packed("padded_to_packed", dev, inputs_padded, first_idxs, int(num_inputs), B, M, D, out)
     return out
 
 
 # reference: csrc/sample_pdf/sample_pdf.h:58-78 -- in place on `outputs`, returns None
 def sample_pdf(bins, weights, outputs, eps: float):
     dev = _require_gpu(bins, weights, outputs)
-    if bins.dtype != torch.float32 or weights.dtype != torch.float32 or outputs.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float")
-    if not outputs.is_contiguous():
-        raise RuntimeError("outputs must be contiguous")  # CHECK_CONTIGUOUS (sample_pdf.h:74)
-    bins, weights = bins.contiguous(), weights.contiguous()
+    bins, weights = _f32c(bins, "bins"), _f32c(weights, "weights")
+    _f32c(outputs, "outputs", copy=False)  # CHECK_CONTIGUOUS (sample_pdf.h:74): written in place
     batch, n_bins = weights.shape
     if bins.shape != (batch, n_bins + 1) or outputs.shape[0] != batch:
         raise RuntimeError("sample_pdf: inconsistent shapes")
-    with _on(dev):
-        _check(
-            _lib.pointops_sample_pdf(bins.data_ptr(), weights.data_ptr(), outputs.data_ptr(), batch, n_bins,
-                                     outputs.shape[1], float(eps), _stream()),
-            "sample_pdf",
-        )
+    _call.sample_pdf("sample_pdf", dev, bins, weights, outputs, batch, n_bins, outputs.shape[1], float(eps))
 
 
 # --- fused device half of get_point_covariances (functions/utils.py:111-153) -------
@@ -498,10 +484,8 @@ def point_covariances(knn):
     dev = _require_gpu(knn)
     knn = knn.contiguous()
     N, P, K, D = knn.shape
-    with _on(dev):
-        cov = torch.empty((N, P, D, D), dtype=torch.float32, device=dev)
-        _check(_lib.pointops_point_covariances(knn.data_ptr(), N, P, K, D, cov.data_ptr(), _stream()),
-               "point_covariances")
+    cov = torch.empty((N, P, D, D), dtype=torch.float32, device=dev)
+    _call.point_covariances("point_covariances", dev, knn, N, P, K, D, cov)
     return cov
 
 
@@ -509,11 +493,8 @@ def point_covariances_backward(knn, grad_cov):
     dev = _require_gpu(knn, grad_cov)
     knn, grad_cov = knn.contiguous(), grad_cov.contiguous()
     N, P, K, D = knn.shape
-    with _on(dev):
-        grad_knn = torch.empty_like(knn)
-        _check(_lib.pointops_point_covariances_backward(knn.data_ptr(), grad_cov.data_ptr(), N, P, K, D,
-                                                        grad_knn.data_ptr(), _stream()),
-               "point_covariances_backward")
+    grad_knn = torch.empty_like(knn)
+    _call.point_covariances_backward("point_covariances_backward", dev, knn, grad_cov, N, P, K, D, grad_knn)
     return grad_knn
 
 
@@ -525,13 +506,10 @@ def local_frames(points, lengths, idx, disambiguate: bool):
     N, P, D = points.shape
     if D != 3 or idx.dim() != 3 or idx.shape[:2] != (N, P) or lengths.shape != (N,):
         raise RuntimeError("local_frames: need points (N,P,3), lengths (N,) and idx (N,P,K)")
-    with _on(dev):
-        curvatures = torch.empty((N, P, 3), dtype=torch.float32, device=dev)
-        frames = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
-        _check(_lib.pointops_local_frames(points.data_ptr(), lengths.data_ptr(), idx.data_ptr(), N, P, idx.shape[2],
-                                          int(bool(disambiguate)), curvatures.data_ptr(), frames.data_ptr(),
-                                          _stream()),
-               "local_frames")
+    curvatures = torch.empty((N, P, 3), dtype=torch.float32, device=dev)
+    frames = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
+    _call.local_frames("local_frames", dev, points, lengths, idx, N, P, idx.shape[2], bool(disambiguate), curvatures,
+                       frames)
     return curvatures, frames
 
 
@@ -545,13 +523,9 @@ def local_frames_backward(curvatures, frames, grad_curvatures, grad_frames, leng
     if (curvatures.shape != (N, P, 3) or grad_curvatures.shape != (N, P, 3) or frames.shape != (N, P, 3, 3)
             or grad_frames.shape != (N, P, 3, 3) or lengths.shape != (N,)):
         raise RuntimeError("local_frames_backward: inconsistent shapes")
-    with _on(dev):
-        grad_cov = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
-        _check(_lib.pointops_local_frames_backward(curvatures.data_ptr(), frames.data_ptr(),
-                                                   grad_curvatures.data_ptr(), grad_frames.data_ptr(),
-                                                   lengths.data_ptr(), N, P, int(bool(disambiguate)),
-                                                   grad_cov.data_ptr(), _stream()),
-               "local_frames_backward")
+    grad_cov = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
+    _call.local_frames_backward("local_frames_backward", dev, curvatures, frames, grad_curvatures, grad_frames, lengths,
+                                N, P, bool(disambiguate), grad_cov)
     return grad_cov
 
 
@@ -568,12 +542,9 @@ def points_alignment(X, Y, idx, lengths, weights, estimate_scale: bool, allow_re
     """X (N,P,D), Y (N,P2,D) fp32, idx (N,P) int64 or None (row i of X <-> Y[n, idx[n,i]]; None: Y[n,i]), lengths
     (N,) or None, weights (N,P) or None -> R (N,D,D), T (N,D), s (N,), singular values (N,D) and, with `want_moments`,
     the fp64 moments (N, 3+4D+D*D) the backward starts from (else None)."""
-    opt = [t for t in (idx, lengths, weights) if t is not None]
-    dev = _require_gpu(X, Y, *opt)
-    X, Y = _f32c(X, "X"), _f32c(Y, "Y")
-    idx = _i64c(idx, "idx") if idx is not None else None
-    lengths = _i64c(lengths, "lengths") if lengths is not None else None
-    weights = _f32c(weights, "weights") if weights is not None else None
+    dev = _require_gpu(X, Y, idx, lengths, weights)
+    X, Y, weights = _f32c(X, "X"), _f32c(Y, "Y"), _f32c(weights, "weights")
+    idx, lengths = _i64c(idx, "idx"), _i64c(lengths, "lengths")
     if X.dim() != 3 or Y.dim() != 3:
         raise RuntimeError("points_alignment: X and Y must be 3-dimensional")
     N, P, D = X.shape
@@ -583,41 +554,31 @@ def points_alignment(X, Y, idx, lengths, weights, estimate_scale: bool, allow_re
             or (weights is not None and weights.shape != (N, P))):
         raise RuntimeError("points_alignment: need X (N,P,D), Y (N,P2,D), D in {2,3}, idx (N,P), lengths (N,), "
                            "weights (N,P)")
-    with _on(dev):
-        R = torch.empty((N, D, D), dtype=torch.float32, device=dev)
-        T = torch.empty((N, D), dtype=torch.float32, device=dev)
-        s = torch.empty((N,), dtype=torch.float32, device=dev)
-        sing = torch.empty((N, D), dtype=torch.float32, device=dev)
-        moments = torch.empty((N, alignment_moment_count(D)), dtype=torch.float64, device=dev) if want_moments else None
-        ws_bytes = _lib.pointops_points_alignment_workspace_bytes(N, P, D)
-        ws = _workspace(ws_bytes, dev)
-        _check(_lib.pointops_points_alignment(X.data_ptr(), Y.data_ptr(), _ptr(idx), _ptr(lengths), _ptr(weights), N, P,
-                                              P2, D, int(bool(estimate_scale)), int(bool(allow_reflection)), float(eps),
-                                              R.data_ptr(), T.data_ptr(), s.data_ptr(), _ptr(moments), sing.data_ptr(),
-                                              _ptr(ws), ws_bytes, _stream()),
-               "points_alignment")
+    R = torch.empty((N, D, D), dtype=torch.float32, device=dev)
+    T = torch.empty((N, D), dtype=torch.float32, device=dev)
+    s = torch.empty((N,), dtype=torch.float32, device=dev)
+    sing = torch.empty((N, D), dtype=torch.float32, device=dev)
+    moments = torch.empty((N, alignment_moment_count(D)), dtype=torch.float64, device=dev) if want_moments else None
+    _call.points_alignment("points_alignment", dev, X, Y, idx, lengths, weights, N, P, P2, D, bool(estimate_scale),
+                           bool(allow_reflection), float(eps), R, T, s, moments, sing,
+                           *_scratch(dev, _lib.pointops_points_alignment_workspace_bytes, N, P, D))
     return R, T, s, sing, moments
 
 
 def points_alignment_backward(X, Y, lengths, weights, grad_moments):
     """grad_moments (N, 3+4D+D*D) fp64 -> grad_X, grad_Y (N,P,D) and grad_weights (N,P) (None without weights)."""
-    opt = [t for t in (lengths, weights) if t is not None]
-    dev = _require_gpu(X, Y, grad_moments, *opt)
-    X, Y = _f32c(X, "X"), _f32c(Y, "Y")
-    lengths = _i64c(lengths, "lengths") if lengths is not None else None
-    weights = _f32c(weights, "weights") if weights is not None else None
+    dev = _require_gpu(X, Y, grad_moments, lengths, weights)
+    X, Y, weights = _f32c(X, "X"), _f32c(Y, "Y"), _f32c(weights, "weights")
+    lengths = _i64c(lengths, "lengths")
     N, P, D = X.shape
     if (Y.shape != X.shape or D not in POINTS_ALIGNMENT_DIMS or grad_moments.dtype != torch.float64
             or grad_moments.shape != (N, alignment_moment_count(D))):
         raise RuntimeError("points_alignment_backward: inconsistent shapes")
     grad_moments = grad_moments.contiguous()
-    with _on(dev):
-        grad_X, grad_Y = torch.empty_like(X), torch.empty_like(Y)
-        grad_w = torch.empty_like(weights) if weights is not None else None
-        _check(_lib.pointops_points_alignment_backward(X.data_ptr(), Y.data_ptr(), _ptr(lengths), _ptr(weights),
-                                                       grad_moments.data_ptr(), N, P, D, grad_X.data_ptr(),
-                                                       grad_Y.data_ptr(), _ptr(grad_w), _stream()),
-               "points_alignment_backward")
+    grad_X, grad_Y = torch.empty_like(X), torch.empty_like(Y)
+    grad_w = torch.empty_like(weights) if weights is not None else None
+    _call.points_alignment_backward("points_alignment_backward", dev, X, Y, lengths, weights, grad_moments, N, P, D,
+                                    grad_X, grad_Y, grad_w)
     return grad_X, grad_Y, grad_w
 
 
@@ -642,22 +603,19 @@ class IcpState:
                 or min(N, P1, P2) < 1 or self.lengths_x.shape != (N,) or self.lengths_y.shape != (N,)):
             raise RuntimeError("icp: need X (N,P1,D), Y (N,P2,D) with N, P1, P2 >= 1, D in {2,3} and lengths (N,)")
         self.dev, self.shape = dev, (N, P1, P2, D)
-        self.flags = (int(bool(estimate_scale)), int(bool(allow_reflection)))
+        self.flags = (bool(estimate_scale), bool(allow_reflection))
         self.thr = float(relative_rmse_thr)
         self.steps = 0
         self.searched = False  # the search workspace holds a grid over Y
-        with _on(dev):
-            self.R = torch.empty((max_iterations, N, D, D), dtype=torch.float32, device=dev)
-            self.T = torch.empty((max_iterations, N, D), dtype=torch.float32, device=dev)
-            self.s = torch.empty((max_iterations, N), dtype=torch.float32, device=dev)
-            self.idx = torch.empty((N, P1), dtype=torch.int64, device=dev)
-            self.dists = torch.empty((N, P1), dtype=torch.float32, device=dev)
-            self.rmse = torch.zeros((N,), dtype=torch.float32, device=dev)
-            self.converged = torch.zeros((1,), dtype=torch.int32, device=dev)
-            self.knn_ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, 1, -1)
-            self.knn_ws = _workspace(self.knn_ws_bytes, dev)
-            self.ws_bytes = _lib.pointops_icp_workspace_bytes(N, P1, D)
-            self.ws = _workspace(self.ws_bytes, dev)
+        self.R = torch.empty((max_iterations, N, D, D), dtype=torch.float32, device=dev)
+        self.T = torch.empty((max_iterations, N, D), dtype=torch.float32, device=dev)
+        self.s = torch.empty((max_iterations, N), dtype=torch.float32, device=dev)
+        self.idx = torch.empty((N, P1), dtype=torch.int64, device=dev)
+        self.dists = torch.empty((N, P1), dtype=torch.float32, device=dev)
+        self.rmse = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.converged = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.knn_ws, self.knn_ws_bytes = _scratch(dev, _lib.pointops_knn_workspace_bytes, N, P1, P2, D, 1, -1)
+        self.ws, self.ws_bytes = _scratch(dev, _lib.pointops_icp_workspace_bytes, N, P1, D)
         self.uses_grid = bool(_lib.pointops_knn_uses_grid(N, P1, P2, D, 1, -1))
         self.reuse_grid = bool(reuse_grid) and self.uses_grid
 
@@ -669,76 +627,48 @@ class IcpState:
         if i >= self.R.shape[0]:
             raise RuntimeError("icp: more steps than max_iterations")
         reuse = -1 if not search else (1 if (self.reuse_grid and self.searched) else 0)
-        with _on(self.dev):
-            _check(_lib.pointops_icp_iteration(self.X_init.data_ptr(), self.Xt.data_ptr(), self.Y.data_ptr(),
-                                               self.lengths_x.data_ptr(), self.lengths_y.data_ptr(), N, P1, P2, D,
-                                               self.flags[0], self.flags[1], int(i == 0), reuse, self.thr,
-                                               self.idx.data_ptr(), self.dists.data_ptr(), self.R[i].data_ptr(),
-                                               self.T[i].data_ptr(), self.s[i].data_ptr(), self.rmse.data_ptr(),
-                                               self.converged.data_ptr(), _ptr(self.knn_ws), self.knn_ws_bytes,
-                                               _ptr(self.ws), self.ws_bytes, _stream()),
-                   "icp_iteration")
+        _call.icp_iteration("icp_iteration", self.dev, self.X_init, self.Xt, self.Y, self.lengths_x, self.lengths_y, N,
+                            P1, P2, D, self.flags[0], self.flags[1], i == 0, reuse, self.thr, self.idx, self.dists,
+                            self.R[i], self.T[i], self.s[i], self.rmse, self.converged, self.knn_ws, self.knn_ws_bytes,
+                            self.ws, self.ws_bytes)
         self.searched = self.searched or search
         self.steps = i + 1
 
 
 # --- device halves of knn_gather / masked_gather (functions/knn.py:200-250) -------
 def gather_neighbors(x, idx, lengths=None):
-    dev = _require_gpu(x, idx) if lengths is None else _require_gpu(x, idx, lengths)
-    x, idx = _f32c(x, "x"), _i64c(idx, "idx")
-    lengths = _i64c(lengths, "lengths") if lengths is not None else None
+    dev = _require_gpu(x, idx, lengths)
+    x, idx, lengths = _f32c(x, "x"), _i64c(idx, "idx"), _i64c(lengths, "lengths")
     N, M, U = x.shape
     _, L, K = idx.shape
-    with _on(dev):
-        out = torch.empty((N, L, K, U), dtype=torch.float32, device=dev)
-        _check(
-            _lib.pointops_gather_neighbors(x.data_ptr(), idx.data_ptr(), _ptr(lengths), N, M, U, L, K,
-                                           out.data_ptr(), _stream()),
-            "gather_neighbors",
-        )
+    out = torch.empty((N, L, K, U), dtype=torch.float32, device=dev)
+    _call.gather_neighbors("gather_neighbors", dev, x, idx, lengths, N, M, U, L, K, out)
     return out
 
 
 def gather_neighbors_backward(grad_out, idx, lengths, M: int, deterministic: bool = False):
-    dev = _require_gpu(grad_out, idx) if lengths is None else _require_gpu(grad_out, idx, lengths)
-    grad_out, idx = _f32c(grad_out, "grad_out"), _i64c(idx, "idx")
-    lengths = _i64c(lengths, "lengths") if lengths is not None else None
+    dev = _require_gpu(grad_out, idx, lengths)
+    grad_out, idx, lengths = _f32c(grad_out, "grad_out"), _i64c(idx, "idx"), _i64c(lengths, "lengths")
     N, L, K, U = grad_out.shape
-    with _on(dev):
-        grad_x = torch.empty((N, M, U), dtype=torch.float32, device=dev)
-        if deterministic:  # inverted neighbour table: every row of x sums its addends in table order
-            ws_bytes = _lib.pointops_backward_det_workspace_bytes(N, L, K, M)
-            ws = _workspace(ws_bytes, dev)
-            _check(
-                _lib.pointops_gather_neighbors_backward_det(
-                    grad_out.data_ptr(), idx.data_ptr(), _ptr(lengths),
-                    N, M, U, L, K, grad_x.data_ptr(), _ptr(ws), ws_bytes, _stream()),
-                "gather_neighbors_backward(deterministic)",
-            )
-            return grad_x
-        _check(
-            _lib.pointops_gather_neighbors_backward(grad_out.data_ptr(), idx.data_ptr(), _ptr(lengths), N, M, U, L, K,
-                                                    grad_x.data_ptr(), _stream()),
-            "gather_neighbors_backward",
-        )
+    grad_x = torch.empty((N, M, U), dtype=torch.float32, device=dev)
+    if deterministic:  # inverted neighbour table: every row of x sums its addends in table order
+        entry, what = _call.gather_neighbors_backward_det, "gather_neighbors_backward(deterministic)"
+        scratch = _scratch(dev, _lib.pointops_backward_det_workspace_bytes, N, L, K, M)
+    else:
+        entry, what, scratch = _call.gather_neighbors_backward, "gather_neighbors_backward", ()
+    entry(what, dev, grad_out, idx, lengths, N, M, U, L, K, grad_x, *scratch)
     return grad_x
 
 
 def chamfer_reduce(dists, lengths, weights, mean: bool):
     """dists (N,P) fp32 -> (N,) per-cloud masked sum [* weights] [/ max(len,1)]."""
-    dev = _require_gpu(dists, lengths) if weights is None else _require_gpu(dists, lengths, weights)
-    dists, lengths = _f32c(dists, "dists"), _i64c(lengths, "lengths")
-    weights = _f32c(weights, "weights") if weights is not None else None
+    dev = _require_gpu(dists, lengths, weights)
+    dists, lengths, weights = _f32c(dists, "dists"), _i64c(lengths, "lengths"), _f32c(weights, "weights")
     N, P = dists.shape
     if lengths.shape != (N,) or (weights is not None and weights.shape != (N,)):
         raise RuntimeError("chamfer_reduce: lengths / weights must have shape (N,)")
-    with _on(dev):
-        out = torch.empty((N,), dtype=torch.float32, device=dev)
-        _check(
-            _lib.pointops_chamfer_reduce(dists.data_ptr(), lengths.data_ptr(), _ptr(weights), N, P, int(bool(mean)),
-                                         out.data_ptr(), _stream()),
-            "chamfer_reduce",
-        )
+    out = torch.empty((N,), dtype=torch.float32, device=dev)
+    _call.chamfer_reduce("chamfer_reduce", dev, dists, lengths, weights, N, P, bool(mean), out)
     return out
 
 
@@ -747,17 +677,41 @@ CHAMFER_MAX_FEATURES = 4
 CHAMFER_MAX_CHANNELS = 16
 
 
+class _HostPointers(ctypes.c_void_p * (1 + CHAMFER_MAX_FEATURES)):
+    """HOST array of device pointers (one per feature tensor, or per output: 1 + F), as the chamfer entries take them;
+    data_ptr() lets it stand where a tensor stands in a native call."""
+
+    def data_ptr(self):
+        return ctypes.addressof(self)
+
+
+class _HostChannels(ctypes.c_int64 * CHAMFER_MAX_FEATURES):
+    def data_ptr(self):
+        return ctypes.addressof(self)
+
+
 def _ptr_array(tensors):
-    arr = (ctypes.c_void_p * max(len(tensors), 1))()
+    arr = _HostPointers()  # (null pointers)
     for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr()
+        if t is not None:
+            arr[i] = t.data_ptr()
     return arr
 
 
+def _feature_args(x_feats, y_feats):
+    """The `F, x_feats, y_feats, C` of every chamfer entry, from feature lists _check_chamfer_shapes has passed."""
+    return len(x_feats), _ptr_array(x_feats), _ptr_array(y_feats), _HostChannels(*[t.shape[2] for t in x_feats])
+
+
+def _f32c_list(tensors, name):
+    return [_f32c(t, name) for t in tensors]
+
+
 def _check_chamfer_shapes(N, P1, P2, idx, x_lengths, y_lengths, weights, x_feats, y_feats):
+    """The shape check of all four chamfer wrappers (`idx`: the (N, P1) neighbour table, None where a call has none)."""
     if len(x_feats) != len(y_feats) or len(x_feats) > CHAMFER_MAX_FEATURES:
         raise RuntimeError(f"chamfer: at most {CHAMFER_MAX_FEATURES} feature pairs")
-    if idx.shape != (N, P1) or x_lengths.shape != (N,) or y_lengths.shape != (N,):
+    if (idx is not None and idx.shape != (N, P1)) or x_lengths.shape != (N,) or y_lengths.shape != (N,):
         raise RuntimeError("chamfer: idx must be (N, P1) and the lengths (N,)")
     if weights is not None and weights.shape != (N,):
         raise RuntimeError("chamfer: weights must have shape (N,)")
@@ -771,29 +725,18 @@ def _check_chamfer_shapes(N, P1, P2, idx, x_lengths, y_lengths, weights, x_feats
 def chamfer_forward(dists, idx, x_lengths, y_lengths, weights, x_feats, y_feats, abs_cosine: bool, mean: bool):
     """dists (N,P1) fp32 and idx (N,P1) int64 of the K=1 search -> out (1+F, N): row 0 the point term,
     row 1+f the cosine term of feature f, each already weighted and (for "mean") length-normalised."""
-    opt = [weights] if weights is not None else []
-    dev = _require_gpu(dists, idx, x_lengths, y_lengths, *opt, *x_feats, *y_feats)
-    dists, idx = _f32c(dists, "dists"), _i64c(idx, "idx")
+    dev = _require_gpu(dists, idx, x_lengths, y_lengths, weights, *x_feats, *y_feats)
+    dists, idx, weights = _f32c(dists, "dists"), _i64c(idx, "idx"), _f32c(weights, "weights")
     x_lengths, y_lengths = _i64c(x_lengths, "x_lengths"), _i64c(y_lengths, "y_lengths")
-    weights = _f32c(weights, "weights") if weights is not None else None
-    x_feats = [_f32c(t, "x_feats") for t in x_feats]
-    y_feats = [_f32c(t, "y_feats") for t in y_feats]
+    x_feats, y_feats = _f32c_list(x_feats, "x_feats"), _f32c_list(y_feats, "y_feats")
     N, P1 = dists.shape
     F = len(x_feats)
     P2 = y_feats[0].shape[1] if F else 0
     _check_chamfer_shapes(N, P1, P2, idx, x_lengths, y_lengths, weights, x_feats, y_feats)
-    C = (ctypes.c_int64 * max(F, 1))(*[int(t.shape[2]) for t in x_feats])
-    with _on(dev):
-        out = torch.empty((1 + F, N), dtype=torch.float32, device=dev)
-        ws_bytes = _lib.pointops_chamfer_workspace_bytes(N, P1)
-        ws = _workspace(ws_bytes, dev)
-        _check(
-            _lib.pointops_chamfer_forward(dists.data_ptr(), idx.data_ptr(), x_lengths.data_ptr(),
-                                          y_lengths.data_ptr(), _ptr(weights), N, P1, P2, F,
-                                          _ptr_array(x_feats), _ptr_array(y_feats), C, int(bool(abs_cosine)),
-                                          int(bool(mean)), out.data_ptr(), _ptr(ws), ws_bytes, _stream()),
-            "chamfer_forward",
-        )
+    out = torch.empty((1 + F, N), dtype=torch.float32, device=dev)
+    _call.chamfer_forward("chamfer_forward", dev, dists, idx, x_lengths, y_lengths, weights, N, P1, P2,
+                          *_feature_args(x_feats, y_feats), bool(abs_cosine), bool(mean), out,
+                          *_scratch(dev, _lib.pointops_chamfer_workspace_bytes, N, P1))
     return out
 
 
@@ -802,51 +745,35 @@ def chamfer_backward(x, y, idx, x_lengths, y_lengths, weights, grad_out, norm: i
     """Closed-form gradients of chamfer_forward's outputs: returns (grad_x, grad_y, [grad_x_feat], [grad_y_feat]).
     `into` = (grad_x, grad_y, [grad_x_feat], [grad_y_feat]) buffers that already hold gradients (the other direction's,
     roles swapped): the gradients are ADDED to them (pointops_chamfer_backward_accumulate) and they are returned."""
-    opt = [weights] if weights is not None else []
-    dev = _require_gpu(x, y, idx, grad_out, x_lengths, y_lengths, *opt, *x_feats, *y_feats)
-    x, y, grad_out = _f32c(x, "x"), _f32c(y, "y"), _f32c(grad_out, "grad_out")
-    idx = _i64c(idx, "idx")
-    x_lengths, y_lengths = _i64c(x_lengths, "x_lengths"), _i64c(y_lengths, "y_lengths")
-    weights = _f32c(weights, "weights") if weights is not None else None
-    x_feats = [_f32c(t, "x_feats") for t in x_feats]
-    y_feats = [_f32c(t, "y_feats") for t in y_feats]
+    dev = _require_gpu(x, y, idx, grad_out, x_lengths, y_lengths, weights, *x_feats, *y_feats)
+    x, y, grad_out, weights = _f32c(x, "x"), _f32c(y, "y"), _f32c(grad_out, "grad_out"), _f32c(weights, "weights")
+    idx, x_lengths, y_lengths = _i64c(idx, "idx"), _i64c(x_lengths, "x_lengths"), _i64c(y_lengths, "y_lengths")
+    x_feats, y_feats = _f32c_list(x_feats, "x_feats"), _f32c_list(y_feats, "y_feats")
     N, P1, D = x.shape
     P2 = y.shape[1]
     F = len(x_feats)
     if y.shape[0] != N or y.shape[2] != D or grad_out.shape != (1 + F, N):
         raise RuntimeError("chamfer_backward: inconsistent shapes")
     _check_chamfer_shapes(N, P1, P2, idx, x_lengths, y_lengths, weights, x_feats, y_feats)
-    C = (ctypes.c_int64 * max(F, 1))(*[int(t.shape[2]) for t in x_feats])
-    with _on(dev):
-        if into is None:
-            grad_x = torch.empty_like(x)
-            grad_y = torch.empty_like(y)
-            gxf = [torch.empty_like(t) for t in x_feats]
-            gyf = [torch.empty_like(t) for t in y_feats]
-            entry = _lib.pointops_chamfer_backward
-        else:
-            grad_x, grad_y, gxf, gyf = into
-            gxf, gyf = list(gxf), list(gyf)
-            for g, like in zip([grad_x, grad_y, *gxf, *gyf], [x, y, *x_feats, *y_feats]):
-                if (g.shape != like.shape or g.dtype != torch.float32 or not g.is_contiguous()
-                        or g.device != like.device):
-                    raise RuntimeError("chamfer_backward: `into` buffers must match the inputs (fp32, contiguous)")
-            entry = _lib.pointops_chamfer_backward_accumulate
-        _check(
-            entry(x.data_ptr(), y.data_ptr(), idx.data_ptr(), x_lengths.data_ptr(), y_lengths.data_ptr(),
-                  _ptr(weights), grad_out.data_ptr(), N, P1, P2, D, int(norm),
-                  F, _ptr_array(x_feats), _ptr_array(y_feats), C, int(bool(abs_cosine)), int(bool(mean)),
-                  grad_x.data_ptr(), grad_y.data_ptr(), _ptr_array(gxf), _ptr_array(gyf), _stream()),
-            "chamfer_backward",
-        )
+    if into is None:
+        grad_x, grad_y = torch.empty_like(x), torch.empty_like(y)
+        gxf, gyf = [torch.empty_like(t) for t in x_feats], [torch.empty_like(t) for t in y_feats]
+        entry = _call.chamfer_backward
+    else:
+        grad_x, grad_y, gxf, gyf = into
+        gxf, gyf = list(gxf), list(gyf)
+        for g, like in zip([grad_x, grad_y, *gxf, *gyf], [x, y, *x_feats, *y_feats]):
+            if (g.shape != like.shape or g.dtype != torch.float32 or not g.is_contiguous()
+                    or g.device != like.device):
+                raise RuntimeError("chamfer_backward: `into` buffers must match the inputs (fp32, contiguous)")
+        entry = _call.chamfer_backward_accumulate
+    entry("chamfer_backward", dev, x, y, idx, x_lengths, y_lengths, weights, grad_out, N, P1, P2, D, int(norm),
+          *_feature_args(x_feats, y_feats), bool(abs_cosine), bool(mean), grad_x, grad_y, _ptr_array(gxf),
+          _ptr_array(gyf))
     return grad_x, grad_y, gxf, gyf
 
 
 _BATCH_REDUCTION = {None: 0, "mean": 1, "sum": 2}
-
-
-def grid_cache_enabled() -> bool:
-    return _GRID_CACHE_ON
 
 
 def chamfer_pair_forward(x, y, x_lengths, y_lengths, norm: int, x_feats, y_feats, abs_cosine: bool, mean: bool,
@@ -856,8 +783,7 @@ def chamfer_pair_forward(x, y, x_lengths, y_lengths, norm: int, x_feats, y_feats
     dev = _require_gpu(x, y, x_lengths, y_lengths, *x_feats, *y_feats)
     x, y = _f32c(x, "x"), _f32c(y, "y")
     x_lengths, y_lengths = _i64c(x_lengths, "x_lengths"), _i64c(y_lengths, "y_lengths")
-    x_feats = [_f32c(t, "x_feats") for t in x_feats]
-    y_feats = [_f32c(t, "y_feats") for t in y_feats]
+    x_feats, y_feats = _f32c_list(x_feats, "x_feats"), _f32c_list(y_feats, "y_feats")
     if norm not in (1, 2):
         raise ValueError("Support for 1 or 2 norm.")
     N, P1, D = x.shape
@@ -865,28 +791,15 @@ def chamfer_pair_forward(x, y, x_lengths, y_lengths, norm: int, x_feats, y_feats
     F = len(x_feats)
     if y.shape[0] != N or y.shape[2] != D:
         raise RuntimeError("chamfer_pair_forward: inconsistent shapes")
-    for a, b in zip(x_feats, y_feats):  # (the index shapes are ours; the feature checks are the single direction's)
-        if a.dim() != 3 or b.dim() != 3 or a.shape[:2] != (N, P1) or b.shape[:2] != (N, P2) \
-                or a.shape[2] != b.shape[2] or not 1 <= a.shape[2] <= CHAMFER_MAX_CHANNELS:
-            raise RuntimeError("chamfer: features must be (N, P1, C) / (N, P2, C) with 1 <= C <= "
-                               f"{CHAMFER_MAX_CHANNELS}")
-    if len(x_feats) != len(y_feats) or F > CHAMFER_MAX_FEATURES or x_lengths.shape != (N,) or y_lengths.shape != (N,):
-        raise RuntimeError(f"chamfer: at most {CHAMFER_MAX_FEATURES} feature pairs, lengths of shape (N,)")
-    C = (ctypes.c_int64 * max(F, 1))(*[int(t.shape[2]) for t in x_feats])
+    _check_chamfer_shapes(N, P1, P2, None, x_lengths, y_lengths, None, x_feats, y_feats)
     red = _BATCH_REDUCTION[batch_reduction]
-    with _on(dev):
-        idx_xy = torch.empty((N, P1), dtype=torch.int64, device=dev)
-        idx_yx = torch.empty((N, P2), dtype=torch.int64, device=dev)
-        outs = [torch.empty(() if red else (N,), dtype=torch.float32, device=dev) for _ in range(1 + F)]
-        ws_bytes = _lib.pointops_chamfer_pair_workspace_bytes(N, P1, P2, D, F)
-        ws = _workspace(ws_bytes, dev)
-        _check(
-            _lib.pointops_chamfer_pair_forward(x.data_ptr(), y.data_ptr(), x_lengths.data_ptr(), y_lengths.data_ptr(), N,
-                                               P1, P2, D, int(norm), F, _ptr_array(x_feats), _ptr_array(y_feats), C,
-                                               int(bool(abs_cosine)), int(bool(mean)), red, idx_xy.data_ptr(),
-                                               idx_yx.data_ptr(), _ptr_array(outs), _ptr(ws), ws_bytes, _stream()),
-            "chamfer_pair_forward",
-        )
+    idx_xy = torch.empty((N, P1), dtype=torch.int64, device=dev)
+    idx_yx = torch.empty((N, P2), dtype=torch.int64, device=dev)
+    outs = [torch.empty(() if red else (N,), dtype=torch.float32, device=dev) for _ in range(1 + F)]
+    _call.chamfer_pair_forward("chamfer_pair_forward", dev, x, y, x_lengths, y_lengths, N, P1, P2, D, int(norm),
+                               *_feature_args(x_feats, y_feats), bool(abs_cosine), bool(mean), red, idx_xy, idx_yx,
+                               _ptr_array(outs),
+                               *_scratch(dev, _lib.pointops_chamfer_pair_workspace_bytes, N, P1, P2, D, F))
     return outs, idx_xy, idx_yx
 
 
@@ -894,33 +807,24 @@ def chamfer_pair_backward(x, y, idx_xy, idx_yx, x_lengths, y_lengths, grads, nor
                           abs_cosine: bool, mean: bool, batch_reduction):
     """Gradients of chamfer_pair_forward's 1+F outputs (`grads`: one tensor or None per output) in ONE native call:
     returns (grad_x, grad_y, [grad_x_feat], [grad_y_feat])."""
-    live = [g for g in grads if g is not None]
-    dev = _require_gpu(x, y, idx_xy, idx_yx, x_lengths, y_lengths, *live, *x_feats, *y_feats)
+    dev = _require_gpu(x, y, idx_xy, idx_yx, x_lengths, y_lengths, *grads, *x_feats, *y_feats)
+    x, y, idx_xy, idx_yx = _f32c(x, "x"), _f32c(y, "y"), _i64c(idx_xy, "idx_xy"), _i64c(idx_yx, "idx_yx")
+    x_lengths, y_lengths = _i64c(x_lengths, "x_lengths"), _i64c(y_lengths, "y_lengths")
+    x_feats, y_feats, grads = _f32c_list(x_feats, "x_feats"), _f32c_list(y_feats, "y_feats"), _f32c_list(grads, "grad")
     N, P1, D = x.shape
     P2 = y.shape[1]
     F = len(x_feats)
     red = _BATCH_REDUCTION[batch_reduction]
     want = () if red else (N,)
-    if len(grads) != 1 + F or any(g.shape != want for g in live):
+    if len(grads) != 1 + F or any(g is not None and g.shape != want for g in grads):
         raise RuntimeError("chamfer_pair_backward: one gradient per output, () after a batch reduction, (N,) without")
-    live = [_f32c(g, "grad") for g in live]
-    it = iter(live)
-    garr = (ctypes.c_void_p * (1 + F))(*[None if g is None else next(it).data_ptr() for g in grads])
-    C = (ctypes.c_int64 * max(F, 1))(*[int(t.shape[2]) for t in x_feats])
-    with _on(dev):
-        grad_x = torch.empty_like(x)
-        grad_y = torch.empty_like(y)
-        gxf = [torch.empty_like(t) for t in x_feats]
-        gyf = [torch.empty_like(t) for t in y_feats]
-        ws_bytes = 4 * (1 + F) * N
-        ws = _workspace(ws_bytes, dev)
-        _check(
-            _lib.pointops_chamfer_pair_backward(x.data_ptr(), y.data_ptr(), idx_xy.data_ptr(), idx_yx.data_ptr(),
-                                                x_lengths.data_ptr(), y_lengths.data_ptr(), garr, N, P1, P2, D,
-                                                int(norm), F, _ptr_array(x_feats), _ptr_array(y_feats), C,
-                                                int(bool(abs_cosine)), int(bool(mean)), red, grad_x.data_ptr(),
-                                                grad_y.data_ptr(), _ptr_array(gxf), _ptr_array(gyf), _ptr(ws),
-                                                ws_bytes, _stream()),
-            "chamfer_pair_backward",
-        )
+    if y.shape[0] != N or y.shape[2] != D or idx_yx.shape != (N, P2):
+        raise RuntimeError("chamfer_pair_backward: inconsistent shapes")
+    _check_chamfer_shapes(N, P1, P2, idx_xy, x_lengths, y_lengths, None, x_feats, y_feats)
+    grad_x, grad_y = torch.empty_like(x), torch.empty_like(y)
+    gxf, gyf = [torch.empty_like(t) for t in x_feats], [torch.empty_like(t) for t in y_feats]
+    _call.chamfer_pair_backward("chamfer_pair_backward", dev, x, y, idx_xy, idx_yx, x_lengths, y_lengths,
+                                _ptr_array(grads), N, P1, P2, D, int(norm), *_feature_args(x_feats, y_feats),
+                                bool(abs_cosine), bool(mean), red, grad_x, grad_y, _ptr_array(gxf), _ptr_array(gyf),
+                                *_scratch(dev, _lib.pointops_chamfer_pair_backward_workspace_bytes, N, F))
     return grad_x, grad_y, gxf, gyf

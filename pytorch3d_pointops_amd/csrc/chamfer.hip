@@ -617,6 +617,10 @@ extern "C" int pointops_chamfer_pair_forward(const float* x, const float* y, con
   return check_launch("chamfer_pair_forward");
 }
 
+extern "C" size_t pointops_chamfer_pair_backward_workspace_bytes(int64_t N, int F) {
+  return sizeof(float) * (size_t)((1 + F) * N);  // the per-cloud gradient of every output row
+}
+
 extern "C" int pointops_chamfer_pair_backward(const float* x, const float* y, const int64_t* idx_xy,
                                               const int64_t* idx_yx, const int64_t* x_lengths,
                                               const int64_t* y_lengths, const float* const* grads, int64_t N,
@@ -631,7 +635,7 @@ extern "C" int pointops_chamfer_pair_backward(const float* x, const float* y, co
                    "chamfer_pair_backward: bad sizes");
   POINTOPS_REQUIRE(batch_reduction >= 0 && batch_reduction <= 2, "chamfer_pair_backward: batch_reduction must be 0, 1 or 2");
   if (N == 0) return POINTOPS_OK;
-  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= sizeof(float) * (size_t)((1 + F) * N),
+  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= pointops_chamfer_pair_backward_workspace_bytes(N, F),
                    "chamfer_pair_backward: workspace of (1 + F) * N floats required");
   PairGrads in;
   for (int f = 0; f < 1 + kCfMaxFeat; ++f) in.g[f] = f <= F ? grads[f] : nullptr;

@@ -11,10 +11,41 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def declared_prototypes():
+    """{symbol: (return type, [parameter types])} of every prototype in include/pointops_amd.h, as C type strings
+    without parameter names and with single spaces ("const float* const*", "int64_t", "void*")."""
+    hdr = open(os.path.join(ROOT, "include", "pointops_amd.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"^([A-Za-z_][\w \t]*?[\w*])\s*\b(pointops_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr,
+                                        flags=re.M):
+        assert name not in protos, f"{name} is declared twice"
+        types = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            ctype, pname = re.fullmatch(r"\s*(.*?[\s*])(\w+)\s*", param, flags=re.S).groups()  # (every parameter is named)
+            types.append(" ".join(ctype.split()))
+        protos[name] = (" ".join(ret.split()), types)
+    return protos
+
+
 def declared_symbols():
     hdr = open(os.path.join(ROOT, "include", "pointops_amd.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     return sorted(set(re.findall(r"\b(pointops_[a-z0-9_]+)\s*\(", hdr)))
+
+
+def ctypes_class(ctype, is_return=False):
+    """The ctypes class a C type of the header binds to; an unknown type fails the test."""
+    import ctypes
+
+    if is_return and ctype == "const char*":
+        return ctypes.c_char_p
+    if ctype.endswith("*"):  # every pointer, "T* const*" and "const void*" included
+        return ctypes.c_void_p
+    scalars = {"int64_t": ctypes.c_int64, "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
+               "size_t": ctypes.c_size_t}
+    assert ctype in scalars, f"no ctypes class for the C type {ctype!r}"
+    return scalars[ctype]
 
 
 def test_library_exports_every_declared_symbol():
@@ -31,6 +62,23 @@ def test_library_exports_every_declared_symbol():
     assert lib.pointops_abi_version() == 1
     lib.pointops_target_arch.restype = ctypes.c_char_p
     assert lib.pointops_target_arch() == b"gfx950"
+
+
+def test_ctypes_table_matches_the_header_type_by_type():
+    """_C._SIGNATURES is a hand copy of the header's prototypes, and ctypes converts by it without complaint: a c_int
+    where the header says int64_t, or a missing trailing pointer, would hand a truncated or shifted argument to a kernel
+    launch.  So every return type and every parameter of every prototype is compared, position by position."""
+    from pytorch3d_pointops_amd import _C
+
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols()  # the prototype parser sees every declared symbol
+    assert sorted(_C._SIGNATURES) == sorted(protos)
+    for name, (ret, params) in sorted(protos.items()):
+        restype, argtypes = _C._SIGNATURES[name]
+        assert restype is ctypes_class(ret, is_return=True), f"{name}: returns {ret}, bound as {restype.__name__}"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters declared, {len(argtypes)} bound"
+        for i, (ctype, bound) in enumerate(zip(params, argtypes)):
+            assert bound is ctypes_class(ctype), f"{name}: parameter {i} is {ctype}, bound as {bound.__name__}"
 
 
 def test_code_object_is_gfx950():

@@ -96,10 +96,8 @@ def main():
 
             def search(reuse):
                 N, P1, P2, D = state.shape
-                _C._check(_C._lib.pointops_knn_points_idx_reuse(
-                    state.Xt.data_ptr(), state.Y.data_ptr(), lengths.data_ptr(), lengths.data_ptr(), N, P1, P2, D, 2,
-                    1, -1, state.idx.data_ptr(), state.dists.data_ptr(), _C._ptr(state.knn_ws), state.knn_ws_bytes,
-                    reuse, _C._stream()), "knn")
+                _C._call.knn_points_idx_reuse("knn", state.dev, state.Xt, state.Y, lengths, lengths, N, P1, P2, D, 2, 1, -1,
+                                              state.idx, state.dists, state.knn_ws, state.knn_ws_bytes, reuse)
 
             row["knn_ms"] = timeit(lambda: search(0))
             row["knn_reuse_ms"] = timeit(lambda: search(1 if state.uses_grid else 0))
