@@ -354,7 +354,8 @@ int pointops_points_alignment_backward(const float* X, const float* Y, const int
  * Y (N,P2,D) (pointops_knn_points_idx_reuse, version -1, on `knn_workspace` of pointops_knn_workspace_bytes(N,P1,P2,D,
  * 1,-1) bytes), the alignment of X_init to Y[idx] weighted by the validity mask of lengths_x (eps 1e-9), Xt = s X_init R
  * + T (fp32; rows >= lengths_x[n] zero) written IN PLACE over the queries, and
- *   rmse[n] = sqrt(sum_valid |Xt - Y[idx]|^2 / max(lengths_x[n], 1e-9))       (in: the previous iteration's, out: this one's)
+ *   rmse[n] = sqrt(sum_valid |Xt - Y[idx]|^2 / max(lengths_x[n], 1e-9))       (in/out: the previous iteration's on entry -- not
+ *   used when `first` != 0, so the first call may pass an uninitialised buffer --, this one's on return)
  *   converged[0] = 1 when (prev - rmse) / prev <= relative_rmse_thr for every cloud, else 0; the change counts as 1
  *   when `first` != 0 and as 0 where prev == 0 (an empty or exactly matched cloud has nothing left to gain).
  *   reuse: 0 = build the search structure; 1 = the caller vouches that Y, lengths_y and the shape are those of the

@@ -216,6 +216,14 @@ _call = types.SimpleNamespace(**{name[len("pointops_"):]: _bind(name, args) for 
                                  if res is _int and args and args[-1] is _vp})
 
 
+# The three names every device buffer that a native call writes comes through -- outputs (_out, _out_like) and scratch
+# (_workspace): uninitialised memory, which the C ABI permits ("outputs are FULLY written by the call", scratch needs no
+# particular contents).  Plain aliases, no Python frame (these calls are host-bound: tools/host_overhead.py);
+# tests/buffers.py patches them to hand out guarded, poisoned buffers.
+_out = torch.empty
+_out_like = torch.empty_like
+
+
 def _workspace(nbytes: int, dev):
     """Device scratch of one native call, or None when it needs none.  A fresh tensor per call: the caching allocator
     is stream-ordered (the block is handed out again only behind this call's launches), and inside a HIP-graph capture
@@ -307,8 +315,8 @@ def knn_points_idx(p1, p2, lengths1, lengths2, norm: int, K: int, version: int =
     if p2.shape[0] != N or p2.shape[2] != D or lengths1.shape != (N,) or lengths2.shape != (N,):
         raise RuntimeError("knn_points_idx: inconsistent shapes")
     K, version = int(K), int(version)
-    idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    idxs = _out((N, P1, K), dtype=torch.int64, device=dev)
+    dists = _out((N, P1, K), dtype=torch.float32, device=dev)
     ws_bytes = _lib.pointops_knn_workspace_bytes(N, P1, P2, D, K, version)
     with _on(dev):  # (the cache keys on the current stream of `dev`)
         if _GRID_CACHE_ON and ws_bytes and _lib.pointops_knn_uses_grid(N, P1, P2, D, K, version) \
@@ -335,9 +343,9 @@ def _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, out_shape, read, what
     K = int(K)
     if not knn_check_version(3, D, K):
         raise RuntimeError("grid family needs D <= 3 and K <= 128")
-    idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
-    out = torch.zeros(out_shape(N), dtype=torch.int32, device=dev)
+    idxs = _out((N, P1, K), dtype=torch.int64, device=dev)
+    dists = _out((N, P1, K), dtype=torch.float32, device=dev)
+    out = _out(out_shape(N), dtype=torch.int32, device=dev)
     ws, ws_bytes = _scratch(dev, _lib.pointops_knn_workspace_bytes, N, P1, P2, D, K, 3)
     with _on(dev):  # (both calls on one stream)
         _call.knn_points_idx("knn_points_idx", None, p1, p2, lengths1, lengths2, N, P1, P2, D, int(norm), K, 3, idxs,
@@ -383,8 +391,8 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm: int, grad_dists,
     if (p2.shape[0] != N or p2.shape[2] != D or idxs.shape != (N, P1, K) or grad_dists.shape != (N, P1, K)
             or lengths1.shape != (N,) or lengths2.shape != (N,)):
         raise RuntimeError("knn_points_backward: inconsistent shapes")
-    grad_p1 = torch.empty((N, P1, D), dtype=torch.float32, device=dev)
-    grad_p2 = torch.empty((N, P2, D), dtype=torch.float32, device=dev)
+    grad_p1 = _out((N, P1, D), dtype=torch.float32, device=dev)
+    grad_p2 = _out((N, P2, D), dtype=torch.float32, device=dev)
     if deterministic:
         entry, what = _call.knn_points_backward_det, "knn_points_backward(deterministic)"
         scratch = _scratch(dev, _lib.pointops_backward_det_workspace_bytes, N, P1, K, P2)
@@ -409,8 +417,8 @@ def ball_query(p1, p2, lengths1, lengths2, K: int, radius: float):
     K = int(K)
     if K < 0:
         raise RuntimeError("ball_query: K must be non-negative")
-    idxs = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    idxs = _out((N, P1, K), dtype=torch.int64, device=dev)
+    dists = _out((N, P1, K), dtype=torch.float32, device=dev)
     _call.ball_query("ball_query", dev, p1, p2, lengths1, lengths2, N, P1, P2, D, K, float(radius), idxs, dists,
                      *_scratch(dev, _lib.pointops_ball_query_workspace_bytes, N, P1, P2, D, K))
     return idxs, dists
@@ -431,7 +439,7 @@ def sample_farthest_points(points, lengths, K, start_idxs, max_K=None):
     if max_K is None:
         max_K = int(K.max().item()) if N > 0 else 0
     max_K = int(max_K) if N > 0 else 0
-    idxs = torch.empty((N, max_K), dtype=torch.int64, device=dev)
+    idxs = _out((N, max_K), dtype=torch.int64, device=dev)
     _call.sample_farthest_points("sample_farthest_points", dev, points, lengths, K, start_idxs, N, P, D, max_K, idxs,
                                  *_scratch(dev, _lib.pointops_fps_workspace_bytes, N, P, max_K))
     return idxs
@@ -446,7 +454,7 @@ def packed_to_padded(inputs_packed, first_idxs, max_size: int):
     _contig(first_idxs, "first_idxs")
     F, D = inputs_packed.shape
     B = first_idxs.shape[0]
-    out = torch.empty((B, max_size, D), dtype=torch.float32, device=dev)
+    out = _out((B, max_size, D), dtype=torch.float32, device=dev)
     _call.packed_to_padded("packed_to_padded", dev, inputs_packed, first_idxs, F, B, int(max_size), D, out)
     return out
 
@@ -459,7 +467,7 @@ def padded_to_packed(inputs_padded, first_idxs, num_inputs: int):
     _contig(inputs_padded, "inputs_padded")
     _contig(first_idxs, "first_idxs")
     B, M, D = inputs_padded.shape
-    out = torch.empty((int(num_inputs), D), dtype=torch.float32, device=dev)
+    out = _out((int(num_inputs), D), dtype=torch.float32, device=dev)
     _call.padded_to_packed("padded_to_packed", dev, inputs_padded, first_idxs, int(num_inputs), B, M, D, out)
     return out
 
@@ -484,7 +492,7 @@ def point_covariances(knn):
     dev = _require_gpu(knn)
     knn = knn.contiguous()
     N, P, K, D = knn.shape
-    cov = torch.empty((N, P, D, D), dtype=torch.float32, device=dev)
+    cov = _out((N, P, D, D), dtype=torch.float32, device=dev)
     _call.point_covariances("point_covariances", dev, knn, N, P, K, D, cov)
     return cov
 
@@ -493,7 +501,7 @@ def point_covariances_backward(knn, grad_cov):
     dev = _require_gpu(knn, grad_cov)
     knn, grad_cov = knn.contiguous(), grad_cov.contiguous()
     N, P, K, D = knn.shape
-    grad_knn = torch.empty_like(knn)
+    grad_knn = _out_like(knn)
     _call.point_covariances_backward("point_covariances_backward", dev, knn, grad_cov, N, P, K, D, grad_knn)
     return grad_knn
 
@@ -506,8 +514,8 @@ def local_frames(points, lengths, idx, disambiguate: bool):
     N, P, D = points.shape
     if D != 3 or idx.dim() != 3 or idx.shape[:2] != (N, P) or lengths.shape != (N,):
         raise RuntimeError("local_frames: need points (N,P,3), lengths (N,) and idx (N,P,K)")
-    curvatures = torch.empty((N, P, 3), dtype=torch.float32, device=dev)
-    frames = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
+    curvatures = _out((N, P, 3), dtype=torch.float32, device=dev)
+    frames = _out((N, P, 3, 3), dtype=torch.float32, device=dev)
     _call.local_frames("local_frames", dev, points, lengths, idx, N, P, idx.shape[2], bool(disambiguate), curvatures,
                        frames)
     return curvatures, frames
@@ -523,7 +531,7 @@ def local_frames_backward(curvatures, frames, grad_curvatures, grad_frames, leng
     if (curvatures.shape != (N, P, 3) or grad_curvatures.shape != (N, P, 3) or frames.shape != (N, P, 3, 3)
             or grad_frames.shape != (N, P, 3, 3) or lengths.shape != (N,)):
         raise RuntimeError("local_frames_backward: inconsistent shapes")
-    grad_cov = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev)
+    grad_cov = _out((N, P, 3, 3), dtype=torch.float32, device=dev)
     _call.local_frames_backward("local_frames_backward", dev, curvatures, frames, grad_curvatures, grad_frames, lengths,
                                 N, P, bool(disambiguate), grad_cov)
     return grad_cov
@@ -554,11 +562,11 @@ def points_alignment(X, Y, idx, lengths, weights, estimate_scale: bool, allow_re
             or (weights is not None and weights.shape != (N, P))):
         raise RuntimeError("points_alignment: need X (N,P,D), Y (N,P2,D), D in {2,3}, idx (N,P), lengths (N,), "
                            "weights (N,P)")
-    R = torch.empty((N, D, D), dtype=torch.float32, device=dev)
-    T = torch.empty((N, D), dtype=torch.float32, device=dev)
-    s = torch.empty((N,), dtype=torch.float32, device=dev)
-    sing = torch.empty((N, D), dtype=torch.float32, device=dev)
-    moments = torch.empty((N, alignment_moment_count(D)), dtype=torch.float64, device=dev) if want_moments else None
+    R = _out((N, D, D), dtype=torch.float32, device=dev)
+    T = _out((N, D), dtype=torch.float32, device=dev)
+    s = _out((N,), dtype=torch.float32, device=dev)
+    sing = _out((N, D), dtype=torch.float32, device=dev)
+    moments = _out((N, alignment_moment_count(D)), dtype=torch.float64, device=dev) if want_moments else None
     _call.points_alignment("points_alignment", dev, X, Y, idx, lengths, weights, N, P, P2, D, bool(estimate_scale),
                            bool(allow_reflection), float(eps), R, T, s, moments, sing,
                            *_scratch(dev, _lib.pointops_points_alignment_workspace_bytes, N, P, D))
@@ -575,8 +583,8 @@ def points_alignment_backward(X, Y, lengths, weights, grad_moments):
             or grad_moments.shape != (N, alignment_moment_count(D))):
         raise RuntimeError("points_alignment_backward: inconsistent shapes")
     grad_moments = grad_moments.contiguous()
-    grad_X, grad_Y = torch.empty_like(X), torch.empty_like(Y)
-    grad_w = torch.empty_like(weights) if weights is not None else None
+    grad_X, grad_Y = _out_like(X), _out_like(Y)
+    grad_w = _out_like(weights) if weights is not None else None
     _call.points_alignment_backward("points_alignment_backward", dev, X, Y, lengths, weights, grad_moments, N, P, D,
                                     grad_X, grad_Y, grad_w)
     return grad_X, grad_Y, grad_w
@@ -607,13 +615,13 @@ class IcpState:
         self.thr = float(relative_rmse_thr)
         self.steps = 0
         self.searched = False  # the search workspace holds a grid over Y
-        self.R = torch.empty((max_iterations, N, D, D), dtype=torch.float32, device=dev)
-        self.T = torch.empty((max_iterations, N, D), dtype=torch.float32, device=dev)
-        self.s = torch.empty((max_iterations, N), dtype=torch.float32, device=dev)
-        self.idx = torch.empty((N, P1), dtype=torch.int64, device=dev)
-        self.dists = torch.empty((N, P1), dtype=torch.float32, device=dev)
-        self.rmse = torch.zeros((N,), dtype=torch.float32, device=dev)
-        self.converged = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.R = _out((max_iterations, N, D, D), dtype=torch.float32, device=dev)
+        self.T = _out((max_iterations, N, D), dtype=torch.float32, device=dev)
+        self.s = _out((max_iterations, N), dtype=torch.float32, device=dev)
+        self.idx = _out((N, P1), dtype=torch.int64, device=dev)
+        self.dists = _out((N, P1), dtype=torch.float32, device=dev)
+        self.rmse = _out((N,), dtype=torch.float32, device=dev)  # (read only from the second step on: `first`)
+        self.converged = _out((1,), dtype=torch.int32, device=dev)
         self.knn_ws, self.knn_ws_bytes = _scratch(dev, _lib.pointops_knn_workspace_bytes, N, P1, P2, D, 1, -1)
         self.ws, self.ws_bytes = _scratch(dev, _lib.pointops_icp_workspace_bytes, N, P1, D)
         self.uses_grid = bool(_lib.pointops_knn_uses_grid(N, P1, P2, D, 1, -1))
@@ -641,7 +649,7 @@ def gather_neighbors(x, idx, lengths=None):
     x, idx, lengths = _f32c(x, "x"), _i64c(idx, "idx"), _i64c(lengths, "lengths")
     N, M, U = x.shape
     _, L, K = idx.shape
-    out = torch.empty((N, L, K, U), dtype=torch.float32, device=dev)
+    out = _out((N, L, K, U), dtype=torch.float32, device=dev)
     _call.gather_neighbors("gather_neighbors", dev, x, idx, lengths, N, M, U, L, K, out)
     return out
 
@@ -650,7 +658,7 @@ def gather_neighbors_backward(grad_out, idx, lengths, M: int, deterministic: boo
     dev = _require_gpu(grad_out, idx, lengths)
     grad_out, idx, lengths = _f32c(grad_out, "grad_out"), _i64c(idx, "idx"), _i64c(lengths, "lengths")
     N, L, K, U = grad_out.shape
-    grad_x = torch.empty((N, M, U), dtype=torch.float32, device=dev)
+    grad_x = _out((N, M, U), dtype=torch.float32, device=dev)
     if deterministic:  # inverted neighbour table: every row of x sums its addends in table order
         entry, what = _call.gather_neighbors_backward_det, "gather_neighbors_backward(deterministic)"
         scratch = _scratch(dev, _lib.pointops_backward_det_workspace_bytes, N, L, K, M)
@@ -667,7 +675,7 @@ def chamfer_reduce(dists, lengths, weights, mean: bool):
     N, P = dists.shape
     if lengths.shape != (N,) or (weights is not None and weights.shape != (N,)):
         raise RuntimeError("chamfer_reduce: lengths / weights must have shape (N,)")
-    out = torch.empty((N,), dtype=torch.float32, device=dev)
+    out = _out((N,), dtype=torch.float32, device=dev)
     _call.chamfer_reduce("chamfer_reduce", dev, dists, lengths, weights, N, P, bool(mean), out)
     return out
 
@@ -733,7 +741,7 @@ def chamfer_forward(dists, idx, x_lengths, y_lengths, weights, x_feats, y_feats,
     F = len(x_feats)
     P2 = y_feats[0].shape[1] if F else 0
     _check_chamfer_shapes(N, P1, P2, idx, x_lengths, y_lengths, weights, x_feats, y_feats)
-    out = torch.empty((1 + F, N), dtype=torch.float32, device=dev)
+    out = _out((1 + F, N), dtype=torch.float32, device=dev)
     _call.chamfer_forward("chamfer_forward", dev, dists, idx, x_lengths, y_lengths, weights, N, P1, P2,
                           *_feature_args(x_feats, y_feats), bool(abs_cosine), bool(mean), out,
                           *_scratch(dev, _lib.pointops_chamfer_workspace_bytes, N, P1))
@@ -756,8 +764,8 @@ def chamfer_backward(x, y, idx, x_lengths, y_lengths, weights, grad_out, norm: i
         raise RuntimeError("chamfer_backward: inconsistent shapes")
     _check_chamfer_shapes(N, P1, P2, idx, x_lengths, y_lengths, weights, x_feats, y_feats)
     if into is None:
-        grad_x, grad_y = torch.empty_like(x), torch.empty_like(y)
-        gxf, gyf = [torch.empty_like(t) for t in x_feats], [torch.empty_like(t) for t in y_feats]
+        grad_x, grad_y = _out_like(x), _out_like(y)
+        gxf, gyf = [_out_like(t) for t in x_feats], [_out_like(t) for t in y_feats]
         entry = _call.chamfer_backward
     else:
         grad_x, grad_y, gxf, gyf = into
@@ -793,9 +801,9 @@ def chamfer_pair_forward(x, y, x_lengths, y_lengths, norm: int, x_feats, y_feats
         raise RuntimeError("chamfer_pair_forward: inconsistent shapes")
     _check_chamfer_shapes(N, P1, P2, None, x_lengths, y_lengths, None, x_feats, y_feats)
     red = _BATCH_REDUCTION[batch_reduction]
-    idx_xy = torch.empty((N, P1), dtype=torch.int64, device=dev)
-    idx_yx = torch.empty((N, P2), dtype=torch.int64, device=dev)
-    outs = [torch.empty(() if red else (N,), dtype=torch.float32, device=dev) for _ in range(1 + F)]
+    idx_xy = _out((N, P1), dtype=torch.int64, device=dev)
+    idx_yx = _out((N, P2), dtype=torch.int64, device=dev)
+    outs = [_out(() if red else (N,), dtype=torch.float32, device=dev) for _ in range(1 + F)]
     _call.chamfer_pair_forward("chamfer_pair_forward", dev, x, y, x_lengths, y_lengths, N, P1, P2, D, int(norm),
                                *_feature_args(x_feats, y_feats), bool(abs_cosine), bool(mean), red, idx_xy, idx_yx,
                                _ptr_array(outs),
@@ -821,8 +829,8 @@ def chamfer_pair_backward(x, y, idx_xy, idx_yx, x_lengths, y_lengths, grads, nor
     if y.shape[0] != N or y.shape[2] != D or idx_yx.shape != (N, P2):
         raise RuntimeError("chamfer_pair_backward: inconsistent shapes")
     _check_chamfer_shapes(N, P1, P2, idx_xy, x_lengths, y_lengths, None, x_feats, y_feats)
-    grad_x, grad_y = torch.empty_like(x), torch.empty_like(y)
-    gxf, gyf = [torch.empty_like(t) for t in x_feats], [torch.empty_like(t) for t in y_feats]
+    grad_x, grad_y = _out_like(x), _out_like(y)
+    gxf, gyf = [_out_like(t) for t in x_feats], [_out_like(t) for t in y_feats]
     _call.chamfer_pair_backward("chamfer_pair_backward", dev, x, y, idx_xy, idx_yx, x_lengths, y_lengths,
                                 _ptr_array(grads), N, P1, P2, D, int(norm), *_feature_args(x_feats, y_feats),
                                 bool(abs_cosine), bool(mean), red, grad_x, grad_y, _ptr_array(gxf), _ptr_array(gyf),

@@ -202,8 +202,8 @@ extern "C" int pointops_knn_points_backward_det(const float* p1, const float* p2
                    "knn_points_backward(deterministic): the neighbour table must have fewer than 2^31 entries");
   if (N == 0) return POINTOPS_OK;
   DetWs ws;
-  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, det_carve(&ws, workspace, N, P1, K, P2)),
-                   "knn_points_backward(deterministic): workspace too small");
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, det_carve(&ws, workspace, N, P1, K, P2)),
+                             "knn_points_backward(deterministic): workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   const int rc = det_invert(ws, idxs, lengths1, lengths2, N, P1, K, P2, stream);
   if (rc != POINTOPS_OK) return rc;
@@ -233,8 +233,8 @@ extern "C" int pointops_gather_neighbors_backward_det(const float* grad_out, con
                    "gather_neighbors_backward(deterministic): the neighbour table must have fewer than 2^31 entries");
   if (N == 0 || M == 0) return POINTOPS_OK;
   DetWs ws;
-  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, det_carve(&ws, workspace, N, L, K, M)),
-                   "gather_neighbors_backward(deterministic): workspace too small");
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, det_carve(&ws, workspace, N, L, K, M)),
+                             "gather_neighbors_backward(deterministic): workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   // knn_gather masks k >= lengths[n] (the lengths of the gathered cloud); queries have no lengths here
   const int rc = det_invert(ws, idx, nullptr, lengths, N, L, K, M, stream);

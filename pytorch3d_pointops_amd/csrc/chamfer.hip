@@ -389,8 +389,8 @@ extern "C" int pointops_chamfer_forward(const float* dists, const int64_t* idx, 
   ChamferFeat ft;
   const int rc = cf_fill(&ft, F, x_feats, y_feats, nullptr, nullptr, C);
   if (rc != POINTOPS_OK) return rc;
-  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, pointops_chamfer_workspace_bytes(N, P1)),
-                   "chamfer_forward: workspace too small");
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, pointops_chamfer_workspace_bytes(N, P1)),
+                             "chamfer_forward: workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   const int chunks = cf_chunks(P1);
   hipLaunchKernelGGL(chamfer_forward_kernel, dim3((unsigned)chunks, (unsigned)N), dim3(kCfBlock), 0, stream, dists,
@@ -582,8 +582,8 @@ extern "C" int pointops_chamfer_pair_forward(const float* x, const float* y, con
   POINTOPS_REQUIRE(batch_reduction >= 0 && batch_reduction <= 2, "chamfer_pair_forward: batch_reduction must be 0, 1 or 2");
   // (N = 0 runs through: the searches and reductions return at once, the combine writes 0 after a batch reduction)
   PairWs ws;
-  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, pair_carve(&ws, workspace, N, P1, P2, D, F)),
-                   "chamfer_pair_forward: workspace too small");
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, pair_carve(&ws, workspace, N, P1, P2, D, F)),
+                             "chamfer_pair_forward: workspace too small");
   hipStream_t main_stream = (hipStream_t)stream_;
   PairSide* side = pair_overlap(N, P1, P2, D) ? pair_side() : nullptr;
   void* stream_b = stream_;
@@ -635,8 +635,9 @@ extern "C" int pointops_chamfer_pair_backward(const float* x, const float* y, co
                    "chamfer_pair_backward: bad sizes");
   POINTOPS_REQUIRE(batch_reduction >= 0 && batch_reduction <= 2, "chamfer_pair_backward: batch_reduction must be 0, 1 or 2");
   if (N == 0) return POINTOPS_OK;
-  POINTOPS_REQUIRE(workspace != nullptr && workspace_bytes >= pointops_chamfer_pair_backward_workspace_bytes(N, F),
-                   "chamfer_pair_backward: workspace of (1 + F) * N floats required");
+  POINTOPS_REQUIRE_WORKSPACE(workspace != nullptr &&
+                                 workspace_bytes >= pointops_chamfer_pair_backward_workspace_bytes(N, F),
+                             "chamfer_pair_backward: workspace of (1 + F) * N floats required");
   PairGrads in;
   for (int f = 0; f < 1 + kCfMaxFeat; ++f) in.g[f] = f <= F ? grads[f] : nullptr;
   float* g = (float*)workspace;

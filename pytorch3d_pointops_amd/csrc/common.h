@@ -57,3 +57,12 @@ inline bool workspace_fits(const void* ws, size_t bytes, size_t need) {
       return POINTOPS_EINVAL;              \
     }                                      \
   } while (0)
+
+// the same for a caller's workspace (workspace_fits): the header's code for "workspace too small"
+#define POINTOPS_REQUIRE_WORKSPACE(cond, ...) \
+  do {                                        \
+    if (!(cond)) {                            \
+      pointops::set_error(__VA_ARGS__);       \
+      return POINTOPS_EWORKSPACE;             \
+    }                                         \
+  } while (0)

@@ -645,8 +645,8 @@ extern "C" int pointops_sample_farthest_points(const float* points, const int64_
                    "sample_farthest_points: sizes must fit int32");
   if (N == 0 || max_K == 0) return POINTOPS_OK;
   const size_t need = pointops_fps_workspace_bytes(N, P, max_K);
-  POINTOPS_REQUIRE(workspace_fits(workspace, workspace_bytes, need),
-                   "sample_farthest_points: workspace of %zu bytes required", need);
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, need),
+                             "sample_farthest_points: workspace of %zu bytes required", need);
   int ppt, G;
   fps_plan(N, P, D, &ppt, &G);
   FpsWs ws;

@@ -253,6 +253,34 @@ _LONG = {
 }
 
 
+# the path assertions of the long-list paths, from the grid statistics (also used by test_buffer_contract_gpu.py)
+def _boxed(st, what, frame, fb):
+    _grid_used(st, what, frame, fb)
+    assert int(st[:2, 8].sum()) > 0, (what, st)  # queries handed to the box search, in every frame
+
+
+def _refined(st, what, frame, fb):
+    _grid_used(st, what, frame, fb)
+    assert (st[:2, 9] > 0).all(), (what, st)  # refined cells: a property of the points, in every frame
+    # queries deferred to the box search: those whose 3x3x3 cube is over-full.  With clouds of opposite sign every
+    # query clamps into the corner cell of the points' box: that corner is where cloud 1 (u^5) is densest, while
+    # cloud 0's cluster sits at the centre, out of the corner's cube -- cloud 0 defers nothing there.
+    clouds = [1] if frame.name == "opposite_signs" else [0, 1]
+    assert (st[clouds, 8] > 0).all(), (what, st)
+
+
+def _wave_sorted(st, what, frame, fb):
+    # test_knn_grid_wave_sort_long_lists: the cluster's neighbourhoods exceed what the kernel streams and end in the
+    # all-pairs list (column 7 of cloud 1); every query of the uniform cloud 0 is certified by its cube (D = 3, L2:
+    # the cells are sized for 3-D Euclidean balls; the planar frame's grid is rebuilt over two axes and keeps it)
+    _grid_used(st, what, frame, fb)
+    assert st[1, 7] > 0, (what, st)
+    if ("wave_sort", frame.name) in _PATH_EXCEPTIONS:
+        assert (st[:3, 7] == fb["l1"][:3]).all(), (what, st)  # what the exception claims: every query, all pairs
+    elif fb["p1"].shape[2] == 3:
+        assert st[0, 7] == 0, (what, st)
+
+
 @pytest.mark.parametrize("path,name,frame", _params(_LONG))
 def test_knn_long_lists_in_frames(dev, oracle, monkeypatch, path, name, frame):
     """box_search: K in (32, 64] with grid_long_box=1 -- statistics column 8 counts the queries handed to the box search;
@@ -260,37 +288,13 @@ def test_knn_long_lists_in_frames(dev, oracle, monkeypatch, path, name, frame):
     wave_sort: 64 < K <= 128 is knn_grid_wsort.hip's range (run_grid_search, knn_grid.hip)."""
     b = _long_base(name)
 
-    def boxed(st, what, frame, fb):
-        _grid_used(st, what, frame, fb)
-        assert int(st[:2, 8].sum()) > 0, (what, st)  # queries handed to the box search, in every frame
-
-    def refined(st, what, frame, fb):
-        _grid_used(st, what, frame, fb)
-        assert (st[:2, 9] > 0).all(), (what, st)  # refined cells: a property of the points, in every frame
-        # queries deferred to the box search: those whose 3x3x3 cube is over-full.  With clouds of opposite sign every
-        # query clamps into the corner cell of the points' box: that corner is where cloud 1 (u^5) is densest, while
-        # cloud 0's cluster sits at the centre, out of the corner's cube -- cloud 0 defers nothing there.
-        clouds = [1] if frame.name == "opposite_signs" else [0, 1]
-        assert (st[clouds, 8] > 0).all(), (what, st)
-
-    def wave_sorted(st, what, frame, fb):
-        # test_knn_grid_wave_sort_long_lists: the cluster's neighbourhoods exceed what the kernel streams and end in the
-        # all-pairs list (column 7 of cloud 1); every query of the uniform cloud 0 is certified by its cube (D = 3, L2:
-        # the cells are sized for 3-D Euclidean balls; the planar frame's grid is rebuilt over two axes and keeps it)
-        _grid_used(st, what, frame, fb)
-        assert st[1, 7] > 0, (what, st)
-        if (path, frame.name) in _PATH_EXCEPTIONS:
-            assert (st[:3, 7] == fb["l1"][:3]).all(), (what, st)  # what the exception claims: every query, all pairs
-        elif fb["p1"].shape[2] == 3:
-            assert st[0, 7] == 0, (what, st)
-
     if path == "box_search":
-        _check_knn(dev, oracle, monkeypatch, path, name, b, frame, "grid_long_box=1", 3, "stats", boxed)
+        _check_knn(dev, oracle, monkeypatch, path, name, b, frame, "grid_long_box=1", 3, "stats", _boxed)
     elif path == "refined_cells":
-        _check_knn(dev, oracle, monkeypatch, path, name, b, frame, "", 3, "stats", refined)
+        _check_knn(dev, oracle, monkeypatch, path, name, b, frame, "", 3, "stats", _refined)
     else:
         assert 64 < b["K"] <= 128
-        _check_knn(dev, oracle, monkeypatch, path, name, b, frame, "", 3, "stats", wave_sorted)
+        _check_knn(dev, oracle, monkeypatch, path, name, b, frame, "", 3, "stats", _wave_sorted)
 
 
 def _table_base(table, seed):
