@@ -19,6 +19,8 @@ def full_lengths(n: int, p: int, device) -> torch.Tensor:
     key = (int(n), int(p), str(device))
     t = _LENGTHS_CACHE.get(key)
     if t is None:
+        if torch.compiler.is_compiling():  # a tensor of the traced graph: the cache holds real tensors only
+            return torch.full((n,), p, dtype=torch.int64, device=device)
         if len(_LENGTHS_CACHE) > 64:
             _LENGTHS_CACHE.clear()
         t = torch.full((n,), p, dtype=torch.int64, device=device)
@@ -76,10 +78,11 @@ def point_pair(p1: torch.Tensor, p2: torch.Tensor, lengths1: Optional[torch.Tens
     p1 = p1.contiguous()
     p2 = p1 if same else p2.contiguous()
     n = p1.shape[0]
-    if lengths1 is None:
+    default1 = lengths1 is None
+    if default1:
         lengths1 = full_lengths(n, p1.shape[1], p1.device)
-    if lengths2 is None:
-        lengths2 = full_lengths(n, p2.shape[1], p1.device)
+    if lengths2 is None:  # (a self-query keeps ONE lengths tensor, cached or traced)
+        lengths2 = lengths1 if same and default1 else full_lengths(n, p2.shape[1], p1.device)
     return p1, p2, lengths1, lengths2
 
 

@@ -77,7 +77,8 @@ def _handle_pointcloud_input(points, lengths, features):
     else:
         if lengths.ndim != 1 or lengths.shape[0] != n:
             raise ValueError("Expected lengths to be of shape (N,)")
-        if (lengths.max() if torch.compiler.is_compiling() else lengths_max(lengths)) > p:
+        # a device-to-host read: eager only (a traced graph skips the check; the kernels clamp every length to P)
+        if not torch.compiler.is_compiling() and lengths_max(lengths) > p:
             raise ValueError("A length value was too long")
     if features is not None:
         _feature_dims_ok(features)
@@ -247,10 +248,11 @@ def _direction_composed(x, y, x_lengths, y_lengths, x_features, y_features, name
         cos = F.cosine_similarity(x_features[name], nearest, dim=2, eps=1e-6)
         per_point[name] = 1 - (cos.abs() if abs_cosine else cos)
 
-    if point_reduction in ("sum", "mean") and per_point[""].dtype == torch.float32 and not torch.compiler.is_compiling():
+    if point_reduction in ("sum", "mean") and per_point[""].dtype == torch.float32:
         w32 = None if weights is None else weights.to(torch.float32)
-        done = {k: _masked_point_reduce.apply(v.contiguous(), x_lengths, w32, point_reduction == "mean")
-                for k, v in per_point.items()}
+        # (a traced graph sees the registered op, pytorch3d_pointops_amd/ops.py: the same kernel and closed form)
+        reduce = torch.ops.pointops_amd.chamfer_reduce if torch.compiler.is_compiling() else _masked_point_reduce.apply
+        done = {k: reduce(v.contiguous(), x_lengths, w32, point_reduction == "mean") for k, v in per_point.items()}
     else:
         outside = torch.arange(P1, device=x.device)[None] >= x_lengths[:, None]  # (N, P1) padding mask
         done = {}
@@ -283,9 +285,10 @@ def _chamfer_distance_single_direction(x, y, x_lengths, y_lengths, x_features, y
     """(point term, feature terms or None) of the direction x -> y (reference: functions/chamfer.py:85-189)."""
     names = _direction_names(x, y, x_features, y_features, feature_names)
     N, P1, D = x.shape
-    if weights is not None:
-        if weights.size(0) != N:
-            raise ValueError("weights must be of shape (N,).")
+    if weights is not None and weights.size(0) != N:
+        raise ValueError("weights must be of shape (N,).")
+    if weights is not None and not torch.compiler.is_compiling():
+        # device-to-host reads: eager only (in a traced graph all-zero weights give the same zeros through the kernels)
         if not (weights >= 0).all():
             raise ValueError("weights cannot be negative.")
         if weights.sum() == 0.0:
@@ -341,7 +344,10 @@ def _reduce_batch(terms: _Terms, weights, batch_reduction: Union[str, None]) -> 
         denom = max(n_clouds, 1)
     else:
         total = weights.sum()
-        denom = 1 if total == 0.0 else total
+        if torch.compiler.is_compiling():  # (no host read in a traced graph)
+            denom = torch.where(total == 0.0, torch.ones_like(total), total)
+        else:
+            denom = 1 if total == 0.0 else total
     return terms.map(lambda t: t / denom)
 
 

@@ -173,7 +173,11 @@ def corresponding_points_alignment(
     if _fused(Xt, Yt) and (weights is None or (weights.is_cuda and weights.dtype == torch.float32)):
         differentiable = torch.is_grad_enabled() and (
             Xt.requires_grad or Yt.requires_grad or (weights is not None and weights.requires_grad))
-        if differentiable:
+        if torch.compiler.is_compiling():  # traced graphs see the registered op (pytorch3d_pointops_amd/ops.py)
+            R, T, s, sing, _ = torch.ops.pointops_amd.points_alignment(Xt.contiguous(), Yt.contiguous(), None, lengths,
+                                                                        weights, bool(estimate_scale),
+                                                                        bool(allow_reflection), float(eps))
+        elif differentiable:
             R, T, s, sing = _alignment.apply(Xt, Yt, lengths, weights, bool(estimate_scale), bool(allow_reflection),
                                              float(eps))
         else:
@@ -187,7 +191,7 @@ def corresponding_points_alignment(
             w = w * weights.to(Xt.dtype)
         R, T, s, sing = _alignment_torch(Xt, Yt, w, estimate_scale, allow_reflection, eps)
 
-    if N > 0 and not _capturing(Xt) and not torch.compiler.is_compiling():
+    if N > 0 and not torch.compiler.is_compiling() and not _capturing(Xt):
         few = (num_points < d + 1).any() if containers else torch.tensor(P < d + 1, device=sing.device)
         few, ambiguous = torch.stack((few.to(sing.device), (sing.detach() <= AMBIGUOUS_ROT_SINGULAR_THR).any())).tolist()
         if few:

@@ -21,10 +21,18 @@ def _per_cloud(points, lengths, K, too_large_msg):
     else:
         if lengths.shape != (n,):
             raise ValueError("points and lengths must have same batch dimension.")
-        if lengths_max(lengths) > p:
+        # a device-to-host read: eager only (a traced graph skips the check; the kernels clamp every length to P)
+        if not torch.compiler.is_compiling() and lengths_max(lengths) > p:
             raise ValueError(too_large_msg)
         lengths = batch_vector(lengths, n, points.device, "lengths", "points and lengths must have same batch dimension.")
     return lengths, batch_vector(K, n, points.device, "K", "K and points must have the same batch dimension")
+
+
+@torch.compiler.disable  # host reads in a loop: a traced graph breaks around this call and goes on after it
+def _draw_start_points(start_idxs, lengths) -> None:
+    """One torch.randint draw per cloud, the reference's RNG consumption (:86-89)."""
+    for n in range(lengths.shape[0]):
+        start_idxs[n] = torch.randint(high=lengths[n], size=(1,)).item()
 
 
 def sample_farthest_points(
@@ -44,13 +52,14 @@ def sample_farthest_points(
     lengths, K = _per_cloud(points, lengths, K, "A value in lengths was too large.")
     points = as_f32(points)
     start_idxs = torch.zeros_like(lengths)
-    if random_start_point:  # one torch.randint draw per cloud, the reference's RNG consumption (:86-89)
-        for n in range(points.shape[0]):
-            start_idxs[n] = torch.randint(high=lengths[n], size=(1,)).item()
+    if random_start_point:
+        _draw_start_points(start_idxs, lengths)
 
     with torch.no_grad():
         if torch.compiler.is_compiling():
-            idx = torch.ops.pointops_amd.sample_farthest_points(points, lengths, K, start_idxs)
+            if known_max is None:  # a tensor K: the reference's host read of max(K) (sample_farthest_points.cu:132)
+                known_max = K.max().item() if points.shape[0] else 0
+            idx = torch.ops.pointops_amd.sample_farthest_points(points, lengths, K, start_idxs, known_max)
         else:
             idx = _C.sample_farthest_points(points, lengths, K, start_idxs, max_K=known_max)
     sampled_points = masked_gather(points, idx)

@@ -29,14 +29,16 @@ def sample_pdf(
     is requested, as the reference does)."""
     if torch.is_grad_enabled() and (bins.requires_grad or weights.requires_grad):
         raise NotImplementedError("sample_pdf differentiability.")
-    if weights.min() <= -eps:
+    compiling = torch.compiler.is_compiling()
+    if not compiling and weights.min() <= -eps:  # a device-to-host read: eager only
         raise ValueError("Negative weights provided.")
     n_bins = weights.shape[-1]
     if bins.shape[-1] != n_bins + 1 or bins.shape[:-1] != weights.shape[:-1]:
         raise ValueError("Inconsistent shapes of bins and weights: " + f"{bins.shape}{weights.shape}")
     out = _quantiles(bins.shape[:-1], n_samples, det, bins.device)
     # the kernel turns the quantiles into samples in place
-    _C.sample_pdf(bins.reshape(-1, n_bins + 1), weights.reshape(-1, n_bins), out.view(-1, n_samples), eps)
+    call = torch.ops.pointops_amd.sample_pdf if compiling else _C.sample_pdf  # (the registered op while tracing)
+    call(bins.reshape(-1, n_bins + 1), weights.reshape(-1, n_bins), out.view(-1, n_samples), eps)
     return out
 
 

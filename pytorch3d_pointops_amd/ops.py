@@ -89,14 +89,18 @@ ball_query.register_autograd(_neighbor_grad(6), setup_context=_neighbor_setup(la
 
 # --------------------------------------------------------------------------- farthest point sampling
 @_op(f"{NS}::sample_farthest_points", mutates_args=())
-def sample_farthest_points(points: Tensor, lengths: Tensor, K: Tensor, start_idxs: Tensor) -> Tensor:
-    return _C.sample_farthest_points(points, lengths, K, start_idxs)
+def sample_farthest_points(points: Tensor, lengths: Tensor, K: Tensor, start_idxs: Tensor,
+                           max_K: Optional[int] = None) -> Tensor:
+    return _C.sample_farthest_points(points, lengths, K, start_idxs, max_K=max_K)
 
 
 @sample_farthest_points.register_fake
-def _(points, lengths, K, start_idxs):
-    max_k = torch.library.get_ctx().new_dynamic_size()  # max(K): known only on the device
-    return _like(points, (points.shape[0], max_k), torch.int64)
+def _(points, lengths, K, start_idxs, max_K=None):
+    if points.shape[0] == 0:
+        max_K = 0  # (the wrapper's rule: an empty batch has no columns)
+    elif max_K is None:
+        max_K = torch.library.get_ctx().new_dynamic_size()  # max(K): known only on the device
+    return _like(points, (points.shape[0], max_K), torch.int64)
 
 
 # --------------------------------------------------------------------------- packed <-> padded
@@ -245,6 +249,69 @@ def _local_frames_grad(ctx, grad_curvatures, grad_frames):
 local_frames.register_autograd(_local_frames_grad, setup_context=_local_frames_setup)
 
 
+# --------------------------------------------------------------------------- points alignment
+@_op(f"{NS}::points_alignment", mutates_args=())
+def points_alignment(X: Tensor, Y: Tensor, idx: Optional[Tensor], lengths: Optional[Tensor], weights: Optional[Tensor],
+                     estimate_scale: bool, allow_reflection: bool, eps: float) -> Tuple[Tensor, Tensor, Tensor, Tensor,
+                                                                                         Tensor]:
+    # (always with the fp64 moments: the registered backward starts from them)
+    return _C.points_alignment(X, Y, idx, lengths, weights, estimate_scale, allow_reflection, eps, want_moments=True)
+
+
+@points_alignment.register_fake
+def _(X, Y, idx, lengths, weights, estimate_scale, allow_reflection, eps):
+    N, _, D = X.shape
+    return (_like(X, (N, D, D), torch.float32), _like(X, (N, D), torch.float32), _like(X, (N,), torch.float32),
+            _like(X, (N, D), torch.float32), _like(X, (N, _C.alignment_moment_count(D)), torch.float64))
+
+
+@_op(f"{NS}::points_alignment_backward", mutates_args=())
+def points_alignment_backward(X: Tensor, Y: Tensor, lengths: Optional[Tensor], weights: Optional[Tensor],
+                              grad_moments: Tensor) -> List[Tensor]:
+    gX, gY, gW = _C.points_alignment_backward(X, Y, lengths, weights, grad_moments)
+    return [gX, gY] if gW is None else [gX, gY, gW]  # grad_X, grad_Y, then grad_weights where there are weights
+
+
+@points_alignment_backward.register_fake
+def _(X, Y, lengths, weights, grad_moments):
+    return [_like(t, t.shape) for t in (X, Y, *([] if weights is None else [weights]))]
+
+
+def _alignment_setup(ctx, inputs, output):
+    X, Y, idx, lengths, weights, estimate_scale, allow_reflection, eps = inputs
+    ctx.has_idx = idx is not None
+    ctx.has = (lengths is not None, weights is not None)
+    ctx.save_for_backward(X, Y, output[4], *[t for t in (lengths, weights) if t is not None])
+    ctx.flags = (estimate_scale, allow_reflection, eps)
+
+
+def _alignment_grad(ctx, gR, gT, gs, _gsing, _gmoments):
+    # functions/points_alignment.py `_alignment.backward`: float64 autograd of the N tiny solves, then one kernel
+    from .functions.points_alignment import _solve_from_moments
+
+    if ctx.has_idx:
+        raise RuntimeError("points_alignment: differentiable without idx only (pointops_points_alignment_backward)")
+    X, Y, moments, *rest = ctx.saved_tensors
+    lengths = rest.pop(0) if ctx.has[0] else None
+    weights = rest.pop(0) if ctx.has[1] else None
+    N, P, d = X.shape
+    if N == 0 or P == 0:  # no element at all: the (empty) inputs are their own gradients, no kernel runs
+        return X.detach(), Y.detach(), None, None, (weights.detach() if weights is not None else None), None, None, None
+    has = (lengths > 0)[:, None] if lengths is not None else torch.ones((N, 1), dtype=torch.bool, device=X.device)
+    px = torch.where(has, X[:, 0].double(), 0.0)
+    py = torch.where(has, Y[:, 0].double(), 0.0)
+    with torch.enable_grad():
+        M = moments.detach().clone().requires_grad_(True)
+        outs = _solve_from_moments(M, px, py, d, *ctx.flags)
+        wanted = [(o, g.double()) for o, g in zip(outs, (gR, gT, gs)) if o.requires_grad and g is not None]
+        (gM,) = torch.autograd.grad([o for o, _ in wanted], [M], [g for _, g in wanted])
+    grads = points_alignment_backward(X, Y, lengths, weights, gM)
+    return grads[0], grads[1], None, None, (grads[2] if weights is not None else None), None, None, None
+
+
+points_alignment.register_autograd(_alignment_grad, setup_context=_alignment_setup)
+
+
 # --------------------------------------------------------------------------- chamfer
 @_op(f"{NS}::chamfer_reduce", mutates_args=())
 def chamfer_reduce(dists: Tensor, lengths: Tensor, weights: Optional[Tensor], mean: bool) -> Tensor:
@@ -254,6 +321,28 @@ def chamfer_reduce(dists: Tensor, lengths: Tensor, weights: Optional[Tensor], me
 @chamfer_reduce.register_fake
 def _(dists, lengths, weights, mean):
     return _like(dists, (dists.shape[0],), torch.float32)
+
+
+def _chamfer_reduce_setup(ctx, inputs, output):
+    dists, lengths, weights, mean = inputs
+    ctx.has_w = weights is not None
+    ctx.save_for_backward(lengths, *([weights] if weights is not None else []))
+    ctx.mean, ctx.P = mean, dists.shape[1]
+
+
+def _chamfer_reduce_grad(ctx, g):
+    # the closed form of functions/chamfer.py `_masked_point_reduce`: g[n] * w[n] / clamp(len[n], 1) for i < len[n]
+    lengths = ctx.saved_tensors[0]
+    scale = g.float()
+    if ctx.has_w:
+        scale = scale * ctx.saved_tensors[1]
+    if ctx.mean:
+        scale = scale / lengths.clamp(min=1)
+    mask = torch.arange(ctx.P, device=g.device)[None] < lengths[:, None]
+    return scale[:, None] * mask, None, None, None
+
+
+chamfer_reduce.register_autograd(_chamfer_reduce_grad, setup_context=_chamfer_reduce_setup)
 
 
 @_op(f"{NS}::chamfer_forward", mutates_args=())
