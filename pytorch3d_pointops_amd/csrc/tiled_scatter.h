@@ -131,11 +131,16 @@ __global__ __launch_bounds__(kTiledBlock) void tiled_scatter_kernel(
   int djl[kPer];
   bool don[kPer];
   bool pending = false;  // wave-uniform
+  // Idle lanes of a drain still issue the source's loads (the drain stays wave-uniform), at a placeholder entry whose
+  // value is never used.  It must lie inside the cloud's table: e0 does while the split has rows; a split without
+  // rows (len < S) has e0 == e1, which for a full cloud is R * K -- one row past p1 and grad_dists, and past the
+  // buffers for the last cloud -- so it falls back to entry 0 (the kernel is launched with R * K > 0 only).
+  const int e_idle = e0 < e1 ? e0 : 0;
   auto drain_issue = [&](int first, int count) {
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
       don[q] = q * 64 + lane < count;
-      const int2 se = don[q] ? stage[first + q * 64 + lane] : make_int2(e0, 0);
+      const int2 se = don[q] ? stage[first + q * 64 + lane] : make_int2(e_idle, 0);
       const int e = se.x;
       djl[q] = se.y;
       const int i = dm.shift < 0 ? e : (int)(__umulhi((unsigned)e, dm.magic) >> dm.shift);  // e / K

@@ -1,0 +1,26 @@
+"""division_magic (csrc/tiled_scatter.h) on the host: tests/native/division_magic_main.cpp, compiled with the hipcc and
+flags of pytorch3d_pointops_amd/build.py, once plain and once with the host sanitizers (UBSan + ASan on the host side of
+the translation unit only).  The program launches no kernel and needs no GPU."""
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+from pytorch3d_pointops_amd import build as hip_build
+
+SRC = os.path.join(ROOT, "tests", "native", "division_magic_main.cpp")
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "ubsan+asan"])
+def test_division_magic_is_exact(tmp_path, sanitize):
+    if not os.path.exists(hip_build.HIPCC):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "division_magic")
+    extra = ["-Xarch_host", "-fsanitize=undefined,address", "-Xarch_host", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    cmd = [hip_build.HIPCC] + hip_build.CXXFLAGS + extra + [SRC, "-o", exe]
+    c = subprocess.run(cmd, capture_output=True, text=True)
+    assert c.returncode == 0, " ".join(cmd) + "\n" + c.stdout + c.stderr
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "no mismatch" in r.stdout and "MISMATCH" not in r.stdout
