@@ -371,6 +371,33 @@ int pointops_icp_iteration(const float* X_init, float* Xt, const float* Y, const
                            void* knn_workspace, size_t knn_workspace_bytes, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/*
+ * Fast Point Feature Histograms (Rusu et al. 2009; 33 bins per point, three groups of 11) and the point-pair features
+ * under them, in two fused passes over a neighbour table -- device half of functions/fpfh.py.  The semantics are this
+ * library's own; all arithmetic is unfused fp32 in the order written.
+ *   points (N,P,3), normals (N,P,3) fp32 (used as given, never renormalised); idx (N,P,K) int64: the knn_points or
+ *   ball_query table of the cloud against itself; lengths (N,) or NULL (= P).  1 <= K <= 255, N < 65536.
+ *   Live slots: slot k of row i < lengths[n] is live when j = idx[n,i,k] has 0 <= j < lengths[n], j != i and
+ *   d2 = dp.dp > 0 for dp = p_j - p_i (ball_query's -1 padding, the self match and exact duplicates are dead).
+ *   Pair features of a live slot: d = sqrtf(d2), a1 = n_i.dp / d, a2 = n_j.dp / d.  If |a1| < |a2|: ns = n_j,
+ *   nt = n_i, dp = -dp, f3 = -a2; otherwise ns = n_i, nt = n_j, f3 = a1.  v = dp x ns; the slot is COUNTED when it is
+ *   live and |v| > 0; then v /= |v|, w = ns x v, f2 = v.nt, f1 = atan2f(w.nt, ns.nt).
+ *   pair_features (N,P,K,4), or NULL: (f1, f2, f3, d) of counted slots, zeros for every other slot and row.
+ *   Bins: b1 = clamp(floorf((f1 + PI_F) * C1_F), 0, 10) with C1_F = (float)(11 / (2 pi)),
+ *   b2 = clamp(floorf((f2 + 1.0f) * 5.5f), 0, 10), b3 likewise from f3; clamped in floating point, so a non-finite
+ *   feature lands in a bin.
+ *   spfh (N,P,33): with m counted slots in the row, spfh[11 c + b_c] = (float)count * (100.0f / (float)m); all zeros
+ *   when m == 0.  Each group of 11 sums to 100 when m > 0.
+ * pointops_fpfh: acc[b] = sum over the live slots in k order of spfh[j][b] / d2, S_c = the sum of acc over group c,
+ *   fpfh (N,P,33)[b] = (S_c > 0 ? acc[b] * 100 / S_c : 0) + spfh[i][b].
+ * Rows i >= lengths[n] are zero in every output.  Outputs are fully written; no workspace, no atomics on global
+ * memory, a fixed summation order: results are bit-reproducible.  N == 0 or P == 0 launches nothing.
+ */
+int pointops_spfh(const float* points, const float* normals, const int64_t* idx, const int64_t* lengths, int64_t N,
+                  int64_t P, int64_t K, float* pair_features, float* spfh, void* stream);
+int pointops_fpfh(const float* points, const int64_t* idx, const int64_t* lengths, const float* spfh, int64_t N,
+                  int64_t P, int64_t K, float* fpfh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
