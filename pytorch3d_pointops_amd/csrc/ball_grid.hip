@@ -349,9 +349,7 @@ int ball_grid_run(const KnnArgs& a, float radius, void* workspace, const int** f
   b.refine = -1;
   const int rc = grid_build(a, ws, b);
   if (rc != POINTOPS_OK) return rc;
-  int64_t chunks = (int64_t)a.N * ceil_div(a.P1, kGridWave);  // one chunk of 64 queries per workgroup (see knn_grid_search.h)
-  chunks = (chunks + 7) / 8 * 8;
-  const int wgs = (int)(chunks < 2048 ? 2048 : (chunks > (1 << 20) ? (1 << 20) : chunks));
+  const int wgs = lane_search_workgroups(a.N, a.P1);
   const float radius2 = radius * radius;  // fp32 product (ball_query_cpu.cpp:26)
   with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) {
     with_bucket(Ints<8, 16, 32, 64>{}, a.K, [&](auto KC) {

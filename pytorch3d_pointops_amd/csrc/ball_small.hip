@@ -10,6 +10,7 @@
 // Padding (-1 / 0) is written by the same wave.  No workspace.
 #include "common.h"
 #include "debug.h"
+#include "knn_common.h"
 #include "knn_grid.h"
 
 #include <algorithm>
@@ -56,16 +57,7 @@ __global__ __launch_bounds__(kBsWaves * 64) void ball_small_kernel(
 #pragma unroll
           for (int u = 0; u < kBsUnroll; ++u) {
             const int j = j0 + u * 64 + lane;
-            float acc;
-            {
-              const float diff = a[0] - c[u][0];
-              acc = diff * diff;
-            }
-#pragma unroll
-            for (int d = 1; d < DT; ++d) {
-              const float diff = a[d] - c[u][d];
-              acc = acc + diff * diff;
-            }
+            const float acc = pair_dist<DT, 2>(a, c[u]);
             const bool hit = j < len2 && acc < radius2;
             const unsigned long long mask = __ballot(hit);
             const int pos = count + __popcll(mask & below);

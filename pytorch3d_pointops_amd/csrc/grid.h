@@ -22,6 +22,14 @@ constexpr int kSortedPad = 32;       // records of padding behind every cloud's 
                                      // up to 7 records past a run's end (G x stride - 1 in the strided walk of the radius-2 pass)
                                      // and stay inside the cloud's array
 
+// Workgroups of a lane search (knn_grid_lane_kernel, ball_grid_lane_kernel): one wave64 per workgroup and ONE chunk of 64
+// queries per workgroup where the launch allows it: the chunk count rounded up to a multiple of 8 (the XCD-aware order)
+// and clamped to [2048, 2^20]; the workgroups loop over the chunks, so any multiple of 8 is correct.
+inline int lane_search_workgroups(int64_t N, int P1) {
+  const int64_t chunks = (N * ceil_div(P1, kGridWave) + 7) / 8 * 8;
+  return (int)(chunks < 2048 ? 2048 : (chunks > (1 << 20) ? (1 << 20) : chunks));
+}
+
 struct GridCloud {
   float lo[3];
   float inv_h;

@@ -305,12 +305,8 @@ int pointops_knn_points_idx_reuse(const float* p1, const float* p2, const int64_
   if (N == 0 || P1 == 0) return POINTOPS_OK;
   POINTOPS_REQUIRE(p1 && p2 && lengths1 && lengths2 && idxs && dists,
                    "knn_points_idx: null pointer");
-  KnnArgs a;
-  a.p1 = p1; a.p2 = p2; a.l1 = lengths1; a.l2 = lengths2;
-  a.P1 = (int)P1; a.P2 = (int)P2; a.D = (int)D; a.K = (int)K; a.N = N;
-  a.tiles = (int)ceil_div(P1, kKnnBlock);
-  a.qlist = nullptr; a.qcount = nullptr;
-  a.idxs = idxs; a.dists = dists; a.stream = (hipStream_t)stream;
+  const KnnArgs a = make_knn_args(p1, p2, lengths1, lengths2, N, P1, P2, D, K, (int)ceil_div(P1, kKnnBlock), idxs, dists,
+                                  (hipStream_t)stream);
   POINTOPS_REQUIRE(N * a.tiles < (1LL << 31), "knn_points_idx: grid too large");
 
   const KnnPlan plan = knn_plan(N, P1, P2, D, K, version);

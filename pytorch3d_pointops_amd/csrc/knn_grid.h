@@ -17,6 +17,12 @@ struct KnnArgs {
   hipStream_t stream;
 };
 
+// the arguments of one call as the C ABI entries receive them (sizes checked to fit int by the caller); no query lists
+inline KnnArgs make_knn_args(const float* p1, const float* p2, const int64_t* l1, const int64_t* l2, int64_t N, int64_t P1,
+                             int64_t P2, int64_t D, int64_t K, int tiles, int64_t* idxs, float* dists, hipStream_t stream) {
+  return KnnArgs{p1, p2, l1, l2, (int)P1, (int)P2, (int)D, (int)K, tiles, N, nullptr, nullptr, idxs, dists, stream};
+}
+
 // The kernel family of one knn_points_idx call (knn.hip), decided once: pointops_knn_workspace_bytes,
 // pointops_knn_uses_grid and the entry all read it.  kNone: nothing to search (N, P1 = 0 or D, K < 1).
 enum class KnnFamily { kNone, kGrid, kWide, kGeneric, kSmall, kScan };

@@ -673,12 +673,10 @@ static inline bool long_lists_to_box(const KnnArgs& a) {
 
 template <int D, int KC, int NORM, int RB>
 static void launch_grid_passes(const KnnArgs& a, const GridWs& ws, bool quad) {
-  // One wave64 per workgroup and ONE chunk of 64 queries per workgroup where the launch allows it (a multiple of 8: the
-  // XCD-aware order): the hardware's workgroup dispatcher then balances the chunks (cfg2, ms per step: 3 840 resident
-  // workgroups looping over their share 0.870, 8 192 0.757, 32 768 = one per chunk 0.731).
-  int64_t chunks = (int64_t)a.N * ceil_div(a.P1, kGridWave);
-  chunks = (chunks + 7) / 8 * 8;
-  const int wgs = (int)(chunks < 2048 ? 2048 : (chunks > (1 << 20) ? (1 << 20) : chunks));
+  // One chunk of 64 queries per workgroup where the launch allows it: the hardware's workgroup dispatcher then balances
+  // the chunks (cfg2, ms per step: 3 840 resident workgroups looping over their share 0.870, 8 192 0.757, 32 768 = one
+  // per chunk 0.731).
+  const int wgs = lane_search_workgroups(a.N, a.P1);
   hipLaunchKernelGGL((knn_grid_lane_kernel<D, KC, NORM, RB>), dim3((unsigned)wgs), dim3(kGridWave), 0, a.stream, a.p1,
                      (const GridCloud*)ws.cloud, (const int*)ws.chunk_prefix, (const float*)ws.edges,
                      (const int*)ws.cell_start, (const float4*)ws.sorted, (const float4*)ws.qsorted, ws.fb_count,

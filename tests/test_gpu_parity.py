@@ -504,6 +504,53 @@ def test_ball_query_grid_adversarial(dev, oracle, monkeypatch, name):
         assert np.array_equal(bits(d.cpu().numpy()), bits(od)), (name, K)
 
 
+_TILE_SCAN_KNOBS = {
+    "storage_order_loop": "ball_grid=0,ball_small=0",
+    "list_staged": "ball_grid=1,ball_factor=1e30",  # (ball_factor=1e30: the device chooses the scan for every cloud)
+    "list_unstaged": "ball_grid=1,ball_factor=1e30,ball_stage=0",
+    "staged_without_lists": "ball_grid=1,ball_factor=1e30,ball_order=0",
+}
+
+
+@pytest.mark.parametrize("D", [1, 2, 3])
+def test_ball_query_tile_scan_sinks_agree(dev, oracle, monkeypatch, D):
+    """The one tile scan of ball_query.hip behind its two sinks (hits stored straight to the rows / staged in LDS), with
+    and without query lists, and the storage-order loop: bit-equal to the oracle and so to each other, at the smallest
+    shape where every branch of the scan runs.  200 points = three full tiles of 64 and a tail of 8, 69 = one tile and
+    a tail of 5, 130 queries = two full waves and two lanes; K = 8 is staged, K = 5 (K % 4 != 0) never is.  Radius 0.15:
+    empty and partly filled rows (the broadcast branch, scans to the end); 0.45: full rows next to unfilled ones (the
+    early exit); 2.0: every point inside every ball, so every full tile takes the dense branch and rows fill inside
+    the first tile."""
+    from pytorch3d_pointops_amd import _C
+
+    p1 = cases.cloud(4101, (2, 130, D))
+    p2 = cases.cloud(4102, (2, 200, D))
+    l1 = np.array([130, 70])
+    l2 = np.array([200, 69])
+    t = [G(x, dev) for x in (p1, p2, l1, l2)]
+    for K in (8, 5):
+        for radius in (0.15, 0.45, 2.0):
+            oi, od = oracle.ball_query(p1, p2, l1, l2, K, radius)
+            if D == 3 and K == 8:  # the inputs still reach the branches named above
+                hits = [(oi[n, : l1[n]] >= 0).sum(axis=1) for n in range(2)]
+                if radius == 0.15:
+                    both = np.concatenate(hits)
+                    assert (both == 0).any() and ((both > 0) & (both < K)).any()
+                elif radius == 0.45:
+                    assert (hits[0] == K).all() and (hits[1] < K).any()
+                else:
+                    full = [oracle.ball_query(p1, p2, l1, l2, 200, radius)[0][n, : l1[n]] for n in range(2)]
+                    assert all(((full[n] >= 0).sum(axis=1) == l2[n]).all() for n in range(2))
+            first = None
+            for name, knob in _TILE_SCAN_KNOBS.items():
+                monkeypatch.setenv("POINTOPS_DEBUG", knob)
+                idx, d = _C.ball_query(*t, K, radius)
+                assert np.array_equal(idx.cpu().numpy(), oi), (name, K, radius)
+                assert np.array_equal(bits(d.cpu().numpy()), bits(od)), (name, K, radius)
+                first = first or (idx, d)
+                assert torch.equal(idx, first[0]) and torch.equal(d.view(torch.int32), first[1].view(torch.int32)), (name, K, radius)
+
+
 # ------------------------------------------------------------------ FPS
 @pytest.mark.parametrize("kernel", ["auto", "clusters"])
 @pytest.mark.parametrize("name", sorted(cases.fps_cases()))
