@@ -220,6 +220,28 @@ __device__ __forceinline__ float box_lower_bound(const GridCloud& g, const float
   return lb;
 }
 
+// The same bound from the six edge-table entries themselves, e = {ed[X0], ed[X1 + 1], ed[kEdgeStride + Y0], ...} in the
+// order of the loads above.  X0 .. Z1 are clamped cell indices, so every one of those entries lies inside the cloud's
+// table whether its face exists or not: a caller loads all six unconditionally, next to its other prologue loads, and
+// the face conditions become selects here -- one batch of loads in place of six dependent round trips.
+template <int NORM>
+__device__ __forceinline__ float box_lower_bound_from(const GridCloud& g, const float (&e)[6], float qx, float qy,
+                                                      float qz, int X0, int X1, int Y0, int Y1, int Z0, int Z1,
+                                                      bool& whole) {
+  const bool hx0 = X0 > 0, hx1 = X1 < g.G[0] - 1;
+  const bool hy0 = Y0 > 0, hy1 = Y1 < g.G[1] - 1;
+  const bool hz0 = Z0 > 0, hz1 = Z1 < g.G[2] - 1;
+  float lb = __builtin_inff();
+  lb = hx0 ? fminf(lb, face_bound<NORM>(qx - prev_float(e[0]))) : lb;
+  lb = hx1 ? fminf(lb, face_bound<NORM>(e[1] - qx)) : lb;
+  lb = hy0 ? fminf(lb, face_bound<NORM>(qy - prev_float(e[2]))) : lb;
+  lb = hy1 ? fminf(lb, face_bound<NORM>(e[3] - qy)) : lb;
+  lb = hz0 ? fminf(lb, face_bound<NORM>(qz - prev_float(e[4]))) : lb;
+  lb = hz1 ? fminf(lb, face_bound<NORM>(e[5] - qz)) : lb;
+  whole = !(hx0 || hx1 || hy0 || hy1 || hz0 || hz1);
+  return lb;
+}
+
 // Candidate threshold seeded from the certification bound lb: only candidates with d < lb can
 // appear in a certified answer (certification needs the KC-th best below lb), so the search may
 // ignore the rest from the first record on.  Distances are non-negative, so bit order = value order.

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_reg_kernel(
     const float* __restrict__ p1, const float* __restrict__ p2,
     const int64_t* __restrict__ lengths1, const int64_t* __restrict__ lengths2, int P1, int P2,
     int K, int tiles_per_cloud, const int* __restrict__ qlist, const int* __restrict__ qcount, int S,
-    unsigned long long* __restrict__ partial, int64_t* __restrict__ idxs, float* __restrict__ dists) {
+    unsigned long long* __restrict__ partial, int vec16, int64_t* __restrict__ idxs, float* __restrict__ dists) {
   const int n = blockIdx.x / tiles_per_cloud;  // wave-uniform
   const int tile = blockIdx.x - n * tiles_per_cloud;
   const int split = blockIdx.y;  // slice of p2 (S > 1: partial lists, merged by knn_merge_kernel)
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_reg_kernel(
   top.init();
   if (S == 1) {
     scan_cloud<D, KC, NORM>(a, p2 + (int64_t)n * P2 * D, 0, len2, top);
-    write_row<KC>(top, K, len2, idxs + row * K, dists + row * K);
+    write_row<KC>(top, K, len2, idxs + row * K, dists + row * K, vec16 != 0);
     return;
   }
   const int jbeg = (int)((int64_t)len2 * split / S), jend = (int)((int64_t)len2 * (split + 1) / S);
@@ -93,8 +93,8 @@ __global__ __launch_bounds__(kKnnBlock) void knn_reg_kernel(
 template <int KC>
 __global__ __launch_bounds__(256) void knn_merge_kernel(
     const unsigned long long* __restrict__ partial, const int64_t* __restrict__ lengths1,
-    const int64_t* __restrict__ lengths2, int P1, int P2, int K, int S, int64_t total, int64_t* __restrict__ idxs,
-    float* __restrict__ dists) {
+    const int64_t* __restrict__ lengths2, int P1, int P2, int K, int S, int64_t total, int vec16,
+    int64_t* __restrict__ idxs, float* __restrict__ dists) {
   const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= total) return;
   const int n = (int)(row / P1), i = (int)(row - (int64_t)n * P1);
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(
       }
     }
   }
-  write_row<KC>(top, K, live ? len2 : 0, idxs + row * K, dists + row * K);
+  write_row<KC>(top, K, live ? len2 : 0, idxs + row * K, dists + row * K, vec16 != 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -190,8 +190,8 @@ void knn_merge_partials(const KnnArgs& a, int S, const void* workspace) {
   const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
   const unsigned long long* ws = (const unsigned long long*)workspace;
   with_bucket(kScanKC, a.K, [&](auto KC) {
-    hipLaunchKernelGGL(knn_merge_kernel<KC>, grid, block, 0, a.stream, ws, a.l1, a.l2, a.P1, a.P2, a.K, S, total, a.idxs,
-                       a.dists);
+    hipLaunchKernelGGL(knn_merge_kernel<KC>, grid, block, 0, a.stream, ws, a.l1, a.l2, a.P1, a.P2, a.K, S, total,
+                       row_stores_16b(a) ? 1 : 0, a.idxs, a.dists);
   });
 }
 
@@ -212,7 +212,7 @@ void launch_knn_bruteforce(const KnnArgs& a, int norm, int splits, void* workspa
       if constexpr (D != 0)  // (any other D has no instance: nothing is launched)
         with_bucket(kScanKC, a.K, [&](auto KC) {
           hipLaunchKernelGGL((knn_reg_kernel<D, KC, NORM>), grid, dim3(block), 0, a.stream, a.p1, a.p2, a.l1, a.l2, a.P1,
-                             a.P2, a.K, tiles, a.qlist, a.qcount, S, partial, a.idxs, a.dists);
+                             a.P2, a.K, tiles, a.qlist, a.qcount, S, partial, row_stores_16b(a) ? 1 : 0, a.idxs, a.dists);
         });
     });
   });

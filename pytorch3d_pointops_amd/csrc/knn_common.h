@@ -132,10 +132,42 @@ __device__ __forceinline__ void scan_cloud(const float (&a)[D], const float* __r
 
 // Write one output row: the first min(K, len2) entries of the list, zeros after
 // (knn_cpu.cpp:25-26 pre-fill).
+//
+// `vec16` (wave-uniform; the host's row_stores_16b(): K % 4 == 0 and both output bases 16-byte aligned, so every row
+// starts on a 16-byte boundary): the row goes out as KC/2 stores of two indices and KC/4 stores of four distances,
+// 16 bytes each, instead of KC 8-byte and KC 4-byte stores.  A piece whose first k is below K lies wholly below K
+// (K is a multiple of the piece), so nothing is written past the row.
 template <int KC, typename TOP>
 __device__ __forceinline__ void write_row(const TOP& top, int K, int len2, int64_t* __restrict__ orow_i,
-                                          float* __restrict__ orow_d) {
+                                          float* __restrict__ orow_d, bool vec16 = false) {
   const int kvalid = len2 < K ? len2 : K;
+  if constexpr (KC % 4 == 0) {
+    if (vec16) {
+      typedef long long i64x2 __attribute__((ext_vector_type(2)));
+      typedef float f32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+      for (int k = 0; k < KC; k += 2) {
+        if (k < K) {
+          i64x2 v;
+          v.x = k < kvalid ? (long long)top.idx_at(k) : 0;
+          v.y = k + 1 < kvalid ? (long long)top.idx_at(k + 1) : 0;
+          *(i64x2*)(orow_i + k) = v;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < KC; k += 4) {
+        if (k < K) {
+          f32x4 v;
+          v.x = k < kvalid ? top.dist_at(k) : 0.0f;
+          v.y = k + 1 < kvalid ? top.dist_at(k + 1) : 0.0f;
+          v.z = k + 2 < kvalid ? top.dist_at(k + 2) : 0.0f;
+          v.w = k + 3 < kvalid ? top.dist_at(k + 3) : 0.0f;
+          *(f32x4*)(orow_d + k) = v;
+        }
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int k = 0; k < KC; ++k) {
     if (k < K) {

@@ -23,6 +23,13 @@ inline KnnArgs make_knn_args(const float* p1, const float* p2, const int64_t* l1
   return KnnArgs{p1, p2, l1, l2, (int)P1, (int)P2, (int)D, (int)K, tiles, N, nullptr, nullptr, idxs, dists, stream};
 }
 
+// Whether the kernels may write the output rows of this call in 16-byte stores (write_row, knn_common.h): then every
+// row idxs + row * K, dists + row * K starts on a 16-byte boundary.  The C ABI promises no alignment of the output
+// buffers, so this is decided per call; a batch slice (knn_grid_run) keeps the alignment of the whole call for such K.
+inline bool row_stores_16b(const KnnArgs& a) {
+  return a.K % 4 == 0 && (((uintptr_t)a.idxs | (uintptr_t)a.dists) & 15u) == 0;
+}
+
 // The kernel family of one knn_points_idx call (knn.hip), decided once: pointops_knn_workspace_bytes,
 // pointops_knn_uses_grid and the entry all read it.  kNone: nothing to search (N, P1 = 0 or D, K < 1).
 enum class KnnFamily { kNone, kGrid, kWide, kGeneric, kSmall, kScan };

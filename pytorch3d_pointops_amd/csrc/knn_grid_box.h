@@ -31,7 +31,7 @@ constexpr int kBoxMaxRecords = 3072;  // a lane never walks more than this: a bi
 
 template <int D, int KC, int NORM, int RB>
 __global__ __launch_bounds__(kGridWave) void knn_grid_box_kernel(
-    const float* __restrict__ p1, GridWs ws, int P1, int P2, int K, int* __restrict__ out_count,
+    const float* __restrict__ p1, GridWs ws, int P1, int P2, int K, int vec16, int* __restrict__ out_count,
     int* __restrict__ out_list, int64_t* __restrict__ idxs, float* __restrict__ dists) {
   constexpr bool kUseQueue = LaneCfg<KC>::kUseQueue;
   constexpr int kQueueCap = LaneCfg<KC>::kQueueLds;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(kGridWave) void knn_grid_box_kernel(
         const unsigned kth_bits = top.kth_bits(K);
         if (kth_bits < 0x7f800000u && __uint_as_float(kth_bits) < lb) {
           const int64_t row = (int64_t)n * P1 + qi;
-          write_row_f64<KC>(top, K, g.len2, idxs + row * K, dists + row * K);
+          write_row_f64<KC>(top, K, g.len2, idxs + row * K, dists + row * K, vec16 != 0);
           done = certified = true;
         }
       }
@@ -200,8 +200,8 @@ static void launch_grid_box(const KnnArgs& a, const GridWs& ws, bool quad) {
   int64_t wx = a.P1 / kGridWave;
   wx = wx < 8 ? 8 : wx > 1024 ? 1024 : wx;
   hipLaunchKernelGGL((knn_grid_box_kernel<D, KC, NORM, RB>), dim3((unsigned)wx, (unsigned)a.N), dim3(kGridWave), 0, a.stream,
-                     a.p1, ws, a.P1, a.P2, a.K, quad ? ws.fb3_count : ws.fb_count, quad ? ws.fb3_list : ws.fb_list, a.idxs,
-                     a.dists);
+                     a.p1, ws, a.P1, a.P2, a.K, row_stores_16b(a) ? 1 : 0, quad ? ws.fb3_count : ws.fb_count,
+                     quad ? ws.fb3_list : ws.fb_list, a.idxs, a.dists);
 }
 
 }  // namespace pointops

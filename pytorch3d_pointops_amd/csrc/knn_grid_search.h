@@ -11,19 +11,12 @@
 
 namespace pointops {
 
-// Write one output row from a TopKF64 list: the first min(K, len2) entries, zeros after (knn_cpu.cpp:25-26).
+// Write one output row from a TopKF64 list: the first min(K, len2) entries, zeros after (knn_cpu.cpp:25-26); `vec16`:
+// in 16-byte stores (write_row, knn_common.h).
 template <int KC>
 __device__ __forceinline__ void write_row_f64(const TopKF64<KC>& top, int K, int len2, int64_t* __restrict__ orow_i,
-                                              float* __restrict__ orow_d) {
-  const int kvalid = len2 < K ? len2 : K;
-#pragma unroll
-  for (int k = 0; k < KC; ++k) {
-    if (k < K) {
-      const bool ok = k < kvalid;
-      orow_i[k] = ok ? (int64_t)top.idx_at(k) : 0;
-      orow_d[k] = ok ? top.dist_at(k) : 0.0f;
-    }
-  }
+                                              float* __restrict__ orow_d, bool vec16) {
+  write_row<KC>(top, K, len2, orow_i, orow_d, vec16);
 }
 
 // ---------------------------------------------------------------------------
@@ -209,7 +202,8 @@ __global__ __launch_bounds__(kGridWave, KC > 32 ? 2 : 1) void knn_grid_lane_kern
     const float* __restrict__ edges, const int* __restrict__ cell_start, const float4* __restrict__ sorted,
     const float4* __restrict__ qsorted, int* __restrict__ fb_count, int* __restrict__ fb_list,
     unsigned* __restrict__ fb_kth, int* __restrict__ box_count, int* __restrict__ box_list, int defer_limit,
-    int uncertified_to_box, int cell_cap, int P1, int P2, int K, int N, int64_t* __restrict__ idxs, float* __restrict__ dists) {
+    int uncertified_to_box, int cell_cap, int P1, int P2, int K, int N, int vec16, int64_t* __restrict__ idxs,
+    float* __restrict__ dists) {
   using Cfg = LaneCfg<KC>;
   constexpr bool kUseQueue = Cfg::kUseQueue;
   constexpr int kQueueCap = Cfg::kQueueLds;
@@ -259,11 +253,28 @@ __global__ __launch_bounds__(kGridWave, KC > 32 ? 2 : 1) void knn_grid_lane_kern
     const int Z0 = max(cz - 1, 0), Z1 = min(cz + 1, g.G[2] - 1);
     const int* __restrict__ cstart = cell_start + (int64_t)n * (cell_cap + 1);
 
+    // Prologue loads, ONE batch: the six edge-table entries of the certification bound and the two cell_start entries
+    // of each of the nine rows, all from clamped indices (valid for every lane: an inactive lane sits at the origin's
+    // cell, a row outside the grid reads its clamped neighbour), the `active` / in-grid conditions applied afterwards
+    // as selects.  (Each load used to sit under its own condition: 15 dependent round trips ahead of the walk.)
+    const float* __restrict__ ed = edges + (int64_t)n * 3 * kEdgeStride;
+    const float edge[6] = {ed[X0], ed[X1 + 1], ed[kEdgeStride + Y0], ed[kEdgeStride + Y1 + 1], ed[2 * kEdgeStride + Z0],
+                           ed[2 * kEdgeStride + Z1 + 1]};
+    constexpr int kDz[kLaneRows] = {0, 0, 0, -1, 1, -1, -1, 1, 1};
+    constexpr int kDy[kLaneRows] = {0, -1, 1, 0, 0, -1, 1, -1, 1};
+    int row_s[kLaneRows], row_e[kLaneRows];
+#pragma unroll
+    for (int r = 0; r < kLaneRows; ++r) {
+      const int z = min(max(cz + kDz[r], 0), g.G[2] - 1), y = min(max(cy + kDy[r], 0), g.G[1] - 1);
+      const int rowbase = (z * g.G[1] + y) * g.G[0];
+      row_s[r] = cstart[rowbase + X0];
+      row_e[r] = cstart[rowbase + X1 + 1];
+    }
+
     // rigorous lower bound of every point outside the lane's cube (certification), known before the
     // walk: it also seeds the candidate threshold
     bool whole;
-    const float lb = box_lower_bound<NORM>(g, edges + (int64_t)n * 3 * kEdgeStride, qx, qy, qz, X0, X1, Y0, Y1, Z0,
-                                           Z1, whole);
+    const float lb = box_lower_bound_from<NORM>(g, edge, qx, qy, qz, X0, X1, Y0, Y1, Z0, Z1, whole);
     const unsigned thr0 = seed_threshold(lb, whole);
 
     // the lane's non-empty runs, own row first (near-first order tightens the thresholds early)
@@ -275,18 +286,14 @@ __global__ __launch_bounds__(kGridWave, KC > 32 ? 2 : 1) void knn_grid_lane_kern
       int total = 0;
 #pragma unroll
       for (int r = 0; r < kLaneRows; ++r) {
-        constexpr int kDz[kLaneRows] = {0, 0, 0, -1, 1, -1, -1, 1, 1};
-        constexpr int kDy[kLaneRows] = {0, -1, 1, 0, 0, -1, 1, -1, 1};
         const int z = cz + kDz[r], y = cy + kDy[r];
-        if (active && z >= 0 && z < g.G[2] && y >= 0 && y < g.G[1]) {
-          const int rowbase = (z * g.G[1] + y) * g.G[0];
-          const int s = cstart[rowbase + X0], e = cstart[rowbase + X1 + 1];
-          if (e > s) {
-            overlong = overlong || e - s > kRunMax;
-            total += e - s;
-            rows[lane + cnt] = ((unsigned)s << kRunBits) | (unsigned)min(e - s, kRunMax);
-            cnt += kGridWave;
-          }
+        const int s = row_s[r], e = row_e[r];
+        const bool listed = active & (z >= 0) & (z < g.G[2]) & (y >= 0) & (y < g.G[1]) & (e > s);
+        if (listed) {
+          overlong = overlong || e - s > kRunMax;
+          total += e - s;
+          rows[lane + cnt] = ((unsigned)s << kRunBits) | (unsigned)min(e - s, kRunMax);
+          cnt += kGridWave;
         }
       }
       overlong = overlong || total > defer_limit;
@@ -307,7 +314,7 @@ __global__ __launch_bounds__(kGridWave, KC > 32 ? 2 : 1) void knn_grid_lane_kern
     if (active) {
       if (ok) {
         const int64_t row = (int64_t)n * P1 + qi;
-        write_row_f64<KC>(top, K, g.len2, idxs + row * K, dists + row * K);
+        write_row_f64<KC>(top, K, g.len2, idxs + row * K, dists + row * K, vec16 != 0);
       } else if (overlong || uncertified_to_box) {
         // (long lists have no quad pass: in big batches their uncertified queries take the box search -- one lane per
         // query, a box sized from the local density -- instead of the wave-per-query search: 1.5 ms of the 5.1 ms at
@@ -388,7 +395,7 @@ __global__ __launch_bounds__(kGridWave, KC >= 32 ? 2 : 1) void knn_grid_quad_ker
     const int* __restrict__ cell_start, const float4* __restrict__ sorted, const int* __restrict__ fb_count,
     const int* __restrict__ fb_list, const unsigned* __restrict__ fb_kth, int* __restrict__ fb3_count,
     int* __restrict__ fb3_list, int* __restrict__ box_count, int* __restrict__ box_list, int cell_cap, int P1, int P2,
-    int K, int64_t* __restrict__ idxs, float* __restrict__ dists) {
+    int K, int vec16, int64_t* __restrict__ idxs, float* __restrict__ dists) {
   constexpr bool kUseQueue = LaneCfg<KC>::kUseQueue;
   constexpr int kQueueCap = LaneCfg<KC>::kQueueLds;
   constexpr int kRunBits = RB, kRunMax = (1 << RB) - 1;
@@ -423,18 +430,39 @@ __global__ __launch_bounds__(kGridWave, KC >= 32 ? 2 : 1) void knn_grid_quad_ker
     // face -> 36 cells instead of 125.  Whatever cube is searched is certified against ITS faces below.
     const float kth3 = __uint_as_float(active ? fb_kth[(int64_t)n * P1 + w] : 0x7f800000u);
     auto reach = [&](bool has, float bound) { return (has && !(kth3 < bound)) ? 2 : 1; };
-    const int ex0 = reach(cx - 1 > 0, face_bound<NORM>(qx - prev_float(ed[max(cx - 1, 0)])));
-    const int ex1 = reach(cx + 1 < g.G[0] - 1, face_bound<NORM>(ed[min(cx + 2, g.G[0])] - qx));
-    const int ey0 = reach(cy - 1 > 0, face_bound<NORM>(qy - prev_float(ed[kEdgeStride + max(cy - 1, 0)])));
-    const int ey1 = reach(cy + 1 < g.G[1] - 1, face_bound<NORM>(ed[kEdgeStride + min(cy + 2, g.G[1])] - qy));
-    const int ez0 = reach(cz - 1 > 0, face_bound<NORM>(qz - prev_float(ed[2 * kEdgeStride + max(cz - 1, 0)])));
-    const int ez1 = reach(cz + 1 < g.G[2] - 1, face_bound<NORM>(ed[2 * kEdgeStride + min(cz + 2, g.G[2])] - qz));
+    // Edge loads, one batch: the faces of the 3x3x3 cube (`near`: they decide the growth) and those one cell further out
+    // (`far`); the faces of the cube that is searched are one or the other, so its bound needs no load of its own.
+    // Order: x low, x high, y low, y high, z low, z high; edge index low = first cell of the cube, high = last cell + 1.
+    const float near[6] = {ed[max(cx - 1, 0)], ed[min(cx + 2, g.G[0])],
+                           ed[kEdgeStride + max(cy - 1, 0)], ed[kEdgeStride + min(cy + 2, g.G[1])],
+                           ed[2 * kEdgeStride + max(cz - 1, 0)], ed[2 * kEdgeStride + min(cz + 2, g.G[2])]};
+    const float far[6] = {ed[max(cx - 2, 0)], ed[min(cx + 3, g.G[0])],
+                          ed[kEdgeStride + max(cy - 2, 0)], ed[kEdgeStride + min(cy + 3, g.G[1])],
+                          ed[2 * kEdgeStride + max(cz - 2, 0)], ed[2 * kEdgeStride + min(cz + 3, g.G[2])]};
+    const int ex0 = reach(cx - 1 > 0, face_bound<NORM>(qx - prev_float(near[0])));
+    const int ex1 = reach(cx + 1 < g.G[0] - 1, face_bound<NORM>(near[1] - qx));
+    const int ey0 = reach(cy - 1 > 0, face_bound<NORM>(qy - prev_float(near[2])));
+    const int ey1 = reach(cy + 1 < g.G[1] - 1, face_bound<NORM>(near[3] - qy));
+    const int ez0 = reach(cz - 1 > 0, face_bound<NORM>(qz - prev_float(near[4])));
+    const int ez1 = reach(cz + 1 < g.G[2] - 1, face_bound<NORM>(near[5] - qz));
     const int X0 = max(cx - ex0, 0), X1 = min(cx + ex1, g.G[0] - 1);
     const int Y0 = max(cy - ey0, 0), Y1 = min(cy + ey1, g.G[1] - 1);
     const int Z0 = max(cz - ez0, 0), Z1 = min(cz + ez1, g.G[2] - 1);
+    // (ed[X0] = ed[max(cx - ex0, 0)] and ed[X1 + 1] = ed[min(cx + ex1 + 1, G)]: the entries loaded above)
+    const float edge[6] = {ex0 == 2 ? far[0] : near[0], ex1 == 2 ? far[1] : near[1], ey0 == 2 ? far[2] : near[2],
+                           ey1 == 2 ? far[3] : near[3], ez0 == 2 ? far[4] : near[4], ez1 == 2 ? far[5] : near[5]};
     bool whole;
-    const float lb = box_lower_bound<NORM>(g, ed, qx, qy, qz, X0, X1, Y0, Y1, Z0, Z1, whole);
+    const float lb = box_lower_bound_from<NORM>(g, edge, qx, qy, qz, X0, X1, Y0, Y1, Z0, Z1, whole);
     const unsigned thr0 = seed_threshold(lb, whole);
+    // cell_start loads, one batch: both ends of all 25 rows from clamped (y, z); rows outside the cube are dropped below
+    int row_s[kQuadRows], row_e[kQuadRows];
+#pragma unroll
+    for (int rr = 0; rr < kQuadRows; ++rr) {
+      const int z = min(max(cz + kQuadDz[rr], 0), g.G[2] - 1), y = min(max(cy + kQuadDy[rr], 0), g.G[1] - 1);
+      const int rowbase = (z * g.G[1] + y) * g.G[0];
+      row_s[rr] = cstart[rowbase + X0];
+      row_e[rr] = cstart[rowbase + X1 + 1];
+    }
 
     // The quad's lanes SHARE every row of the cube: lane `sub` takes the records sub, sub + 4, sub + 8, ... of each of
     // the <= 25 contiguous runs (nearest rows first), so the four gathers of a quad fall into the same 64-byte segment and
@@ -451,9 +479,8 @@ __global__ __launch_bounds__(kGridWave, KC >= 32 ? 2 : 1) void knn_grid_quad_ker
 #pragma unroll
       for (int rr = 0; rr < kQuadRows; ++rr) {
         const int z = cz + kQuadDz[rr], y = cy + kQuadDy[rr];
-        if (active && z >= Z0 && z <= Z1 && y >= Y0 && y <= Y1) {
-          const int rowbase = (z * g.G[1] + y) * g.G[0];
-          const int s = cstart[rowbase + X0], e = cstart[rowbase + X1 + 1];
+        const int s = row_s[rr], e = row_e[rr];
+        if (active & (z >= Z0) & (z <= Z1) & (y >= Y0) & (y <= Y1)) {
           overlong = overlong || e - s > kRunMax;
           total += e - s;
           if (e - s > sub) {  // (the lane's share of the row: records s + sub, s + sub + 4, ... below e)
@@ -487,7 +514,7 @@ __global__ __launch_bounds__(kGridWave, KC >= 32 ? 2 : 1) void knn_grid_quad_ker
     if (active && sub == 0) {
       if (ok) {
         const int64_t row = (int64_t)n * P1 + qi;
-        write_row_f64<KC>(top, K, g.len2, idxs + row * K, dists + row * K);
+        write_row_f64<KC>(top, K, g.len2, idxs + row * K, dists + row * K, vec16 != 0);
       } else if (big) {  // an over-full cell in the cube: the box search knows its inside
         const int pos = atomicAdd(box_count + n, 1);
         box_list[(int64_t)n * P1 + pos] = qi;
@@ -681,7 +708,8 @@ static void launch_grid_passes(const KnnArgs& a, const GridWs& ws, bool quad) {
                      (const GridCloud*)ws.cloud, (const int*)ws.chunk_prefix, (const float*)ws.edges,
                      (const int*)ws.cell_start, (const float4*)ws.sorted, (const float4*)ws.qsorted, ws.fb_count,
                      ws.fb_list, ws.fb_kth, ws.box_count, ws.box_list, kDeferFactor * refine_threshold(ws.c_target),
-                     (KC > 32 && long_lists_to_box(a)) ? 1 : 0, ws.cell_cap, a.P1, a.P2, a.K, (int)a.N, a.idxs, a.dists);
+                     (KC > 32 && long_lists_to_box(a)) ? 1 : 0, ws.cell_cap, a.P1, a.P2, a.K, (int)a.N,
+                     row_stores_16b(a) ? 1 : 0, a.idxs, a.dists);
   if constexpr (KC <= 32) if (quad) {
     int64_t wx = a.P1 / (32 * kQuadQueries);  // a few % of a cloud arrive here
     wx = wx < 8 ? 8 : wx > 4096 ? 4096 : wx;
@@ -689,7 +717,7 @@ static void launch_grid_passes(const KnnArgs& a, const GridWs& ws, bool quad) {
                        a.stream, a.p1, (const GridCloud*)ws.cloud, (const float*)ws.edges, (const int*)ws.cell_start,
                        (const float4*)ws.sorted, (const int*)ws.fb_count, (const int*)ws.fb_list,
                        (const unsigned*)ws.fb_kth, ws.fb3_count, ws.fb3_list, ws.box_count, ws.box_list, ws.cell_cap, a.P1,
-                       a.P2, a.K, a.idxs, a.dists);
+                       a.P2, a.K, row_stores_16b(a) ? 1 : 0, a.idxs, a.dists);
   }
   launch_grid_box<D, KC, NORM, RB>(a, ws, quad);  // over-full neighbourhoods (appends what it cannot certify)
   hipLaunchKernelGGL((knn_grid_wave_kernel<D, KC, NORM>), dim3(kWaveKernelWgsPerCloud, (unsigned)a.N),

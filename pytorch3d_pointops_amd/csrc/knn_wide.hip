@@ -98,7 +98,7 @@ template <int KC, int NORM, int WG>
 __global__ __launch_bounds__(WG) void knn_wide_kernel(
     const float* __restrict__ p1, const float* __restrict__ p2, const int64_t* __restrict__ lengths1,
     const int64_t* __restrict__ lengths2, int P1, int P2, int D, int K, int tiles_per_cloud, int S,
-    unsigned long long* __restrict__ partial, const int* __restrict__ qlist, const int* __restrict__ qcount,
+    unsigned long long* __restrict__ partial, const int* __restrict__ qlist, const int* __restrict__ qcount, int vec16,
     int64_t* __restrict__ idxs, float* __restrict__ dists) {
   extern __shared__ float s_dyn[];
   float* __restrict__ s_q = s_dyn;  // [D][WG]
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(WG) void knn_wide_kernel(
       if (acc[0] < top.worst()) top.insert(acc[0], j);
     }
     if (S == 1) {
-      if (owns_row) write_row<KC>(top, K, live ? len2 : 0, idxs + row * K, dists + row * K);
+      if (owns_row) write_row<KC>(top, K, live ? len2 : 0, idxs + row * K, dists + row * K, vec16 != 0);
     } else if (owns_row) {
       // partial list of this slice as (dist bits, idx) keys; empty slots order last
       unsigned long long* __restrict__ o = partial + (row * S + split) * K;
@@ -265,7 +265,8 @@ static int launch_wide(const KnnArgs& a, size_t lds, int S, void* workspace) {
   const int tiles = (int)ceil_div(a.P1, WG);
   if (a.N * tiles >= (1LL << 31)) return POINTOPS_EINVAL;
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.N * tiles), (unsigned)S), dim3(WG), lds, a.stream, a.p1, a.p2, a.l1, a.l2,
-                     a.P1, a.P2, a.D, a.K, tiles, S, (unsigned long long*)workspace, a.qlist, a.qcount, a.idxs, a.dists);
+                     a.P1, a.P2, a.D, a.K, tiles, S, (unsigned long long*)workspace, a.qlist, a.qcount,
+                     row_stores_16b(a) ? 1 : 0, a.idxs, a.dists);
   if (KC > 0 && KC <= 32 && S > 1) knn_merge_partials(a, S, workspace);
   return POINTOPS_OK;
 }
