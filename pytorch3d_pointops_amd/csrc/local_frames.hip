@@ -24,85 +24,13 @@
 // v_j v_i^T -- the eigh backward; the flips are piecewise constant.  Coincident eigenvalues divide by zero, as
 // torch.linalg.eigh's backward does.  The rest of the chain (gather, covariance backward, scatter) is existing code.
 #include "common.h"
+#include "small_solvers.h"
 
 namespace pointops {
 
 constexpr int kLfTile = 64;           // queries (lanes) per workgroup of the forward
 constexpr int kLfStageMaxK = 64;      // staged form: 64 rows of (3K | 1) floats <= 49.4 KiB of LDS
 constexpr int kLfBwdBlock = 256;
-constexpr int kJacobiMaxSweeps = 12;  // 3x3 cyclic Jacobi converges quadratically: 4-6 sweeps in practice
-constexpr double kJacobiTol = 1e-30;  // stop when sum of squared off-diagonals <= tol * sum of squared diagonals
-
-// One Jacobi rotation zeroing a[P][Q] (Numerical Recipes' form); v accumulates the rotations as columns.
-template <int P, int Q>
-__host__ __device__ __forceinline__ void jacobi_rotate(double (&a)[3][3], double (&v)[3][3]) {
-  constexpr int R = 3 - P - Q;
-  const double apq = a[P][Q];
-  if (apq == 0.0) return;
-  const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-  const double at = fabs(theta);
-  double t = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(at * at + 1.0));
-  if (theta < 0.0) t = -t;
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-  a[P][P] -= t * apq;
-  a[Q][Q] += t * apq;
-  a[P][Q] = a[Q][P] = 0.0;
-  const double arp = a[R][P], arq = a[R][Q];
-  a[R][P] = a[P][R] = arp - s * (arq + tau * arp);
-  a[R][Q] = a[Q][R] = arq + s * (arp - tau * arq);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double g = v[k][P], h = v[k][Q];
-    v[k][P] = g - s * (h + tau * g);
-    v[k][Q] = h + s * (g - tau * h);
-  }
-}
-
-// Stable compare-exchange of eigenpairs I < J (ascending eigenvalues; equal values keep their order).
-template <int I, int J>
-__host__ __device__ __forceinline__ void eig_order(double (&l)[3], double (&v)[3][3]) {
-  if (l[I] > l[J]) {
-    const double t = l[I];
-    l[I] = l[J];
-    l[J] = t;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double u = v[k][I];
-      v[k][I] = v[k][J];
-      v[k][J] = u;
-    }
-  }
-}
-
-// Eigen-decomposition of the symmetric fp32 matrix c: ascending eigenvalues lam, eigenvectors as columns of vec.
-__host__ __device__ __forceinline__ void sym3_eigen(const float (&c)[3][3], float (&lam)[3], float (&vec)[3][3]) {
-  double a[3][3], v[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      a[r][q] = (double)c[r][q];
-      v[r][q] = r == q ? 1.0 : 0.0;
-    }
-  for (int sweep = 0; sweep < kJacobiMaxSweeps; ++sweep) {
-    const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-    const double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
-    if (off <= kJacobiTol * diag) break;  // also ends a zero matrix before any rotation
-    jacobi_rotate<0, 1>(a, v);
-    jacobi_rotate<0, 2>(a, v);
-    jacobi_rotate<1, 2>(a, v);
-  }
-  double l[3] = {a[0][0], a[1][1], a[2][2]};
-  eig_order<0, 1>(l, v);
-  eig_order<1, 2>(l, v);
-  eig_order<0, 1>(l, v);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    lam[r] = (float)l[r];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) vec[r][q] = (float)v[r][q];
-  }
-}
 
 template <bool STAGED>
 __global__ __launch_bounds__(kLfTile) void local_frames_kernel(const float* __restrict__ points,

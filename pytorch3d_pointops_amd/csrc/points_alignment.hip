@@ -25,6 +25,7 @@
 // elementwise alignment_backward_kernel: the gradient of the moments (from the host's float64 autograd of the N tiny
 // solves) pushed to X, Y and the weights.
 #include "common.h"
+#include "small_solvers.h"
 
 namespace pointops {
 
@@ -32,17 +33,6 @@ constexpr int kPaBlock = 256;          // threads per block of the point passes
 constexpr int kPaWaves = kPaBlock / kWave;
 constexpr int kPaRowsPerThread = 8;    // rows per thread before a cloud gets another block
 constexpr int kPaMaxBlocks = 32;       // partials per cloud (the solve sums them one after the other)
-constexpr int kSvdMaxSweeps = 30;      // one-sided Jacobi converges quadratically: 3-5 sweeps in practice
-constexpr double kSvdTol = 1e-15;      // columns count as orthogonal when |a_p . a_q| <= tol |a_p| |a_q|
-constexpr double kSvdNegligible = 1e-12;  // sigma_j <= this * sigma_1: direction j of U comes from orthogonality
-
-__host__ __device__ constexpr int pa_moments(int D) { return 3 + 4 * D + D * D; }
-// moment slots: 0 Sw, 1 Sw2, then D each of Swx, Swy, Sw2x, Sw2y, then D*D of Sxy (row = x), then Sxx
-template <int D>
-struct PaSlot {
-  static constexpr int kSw = 0, kSw2 = 1, kSwx = 2, kSwy = 2 + D, kSw2x = 2 + 2 * D, kSw2y = 2 + 3 * D,
-                       kSxy = 2 + 4 * D, kSxx = 2 + 4 * D + D * D, kCount = 3 + 4 * D + D * D;
-};
 
 inline int pa_blocks(int64_t P) {
   const int64_t nb = ceil_div(P, (int64_t)kPaBlock * kPaRowsPerThread);
@@ -152,206 +142,6 @@ __global__ __launch_bounds__(kPaBlock) void alignment_moments_kernel(
     acc[S::kSxx] += xx;
   }
   pa_block_sum<M>(acc, s_part, partials + ((int64_t)n * nb + blockIdx.x) * M);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// d x d solve (fp64, one lane).  A = C on entry; on exit A V = U S: columns of A are orthogonal.
-template <int D>
-__host__ __device__ __forceinline__ void pa_one_sided_jacobi(double (&A)[D][D], double (&V)[D][D]) {
-#pragma unroll
-  for (int r = 0; r < D; ++r)
-#pragma unroll
-    for (int c = 0; c < D; ++c) V[r][c] = r == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < kSvdMaxSweeps; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < D - 1; ++p)
-#pragma unroll
-      for (int q = p + 1; q < D; ++q) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-#pragma unroll
-        for (int r = 0; r < D; ++r) {
-          alpha += A[r][p] * A[r][p];
-          beta += A[r][q] * A[r][q];
-          gamma += A[r][p] * A[r][q];
-        }
-        if (gamma == 0.0 || fabs(gamma) <= kSvdTol * sqrt(alpha * beta)) continue;
-        rotated = true;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double az = fabs(zeta);
-        double t = az > 1e150 ? 0.5 / az : 1.0 / (az + sqrt(az * az + 1.0));
-        if (zeta < 0.0) t = -t;
-        const double c = 1.0 / sqrt(t * t + 1.0), s = c * t;
-#pragma unroll
-        for (int r = 0; r < D; ++r) {
-          const double ap = A[r][p], aq = A[r][q];
-          A[r][p] = c * ap - s * aq;
-          A[r][q] = s * ap + c * aq;
-          const double vp = V[r][p], vq = V[r][q];
-          V[r][p] = c * vp - s * vq;
-          V[r][q] = s * vp + c * vq;
-        }
-      }
-    if (!rotated) break;
-  }
-}
-
-template <int D>
-__host__ __device__ __forceinline__ void pa_swap_cols(double (&A)[D][D], double (&V)[D][D], double (&sg)[D], int i,
-                                                      int j) {
-  if (sg[i] >= sg[j]) return;  // descending, stable
-  const double t = sg[i];
-  sg[i] = sg[j];
-  sg[j] = t;
-#pragma unroll
-  for (int r = 0; r < D; ++r) {
-    double u = A[r][i];
-    A[r][i] = A[r][j];
-    A[r][j] = u;
-    u = V[r][i];
-    V[r][i] = V[r][j];
-    V[r][j] = u;
-  }
-}
-
-template <int D>
-__host__ __device__ __forceinline__ double pa_det(const double (&m)[D][D]) {
-  if constexpr (D == 2) {
-    return m[0][0] * m[1][1] - m[0][1] * m[1][0];
-  } else {
-    return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
-           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-  }
-}
-
-// C (d x d, fp64) -> singular values sg (descending), U, V with C = U diag(sg) V^T, U and V orthogonal for ANY C:
-// a negligible sigma_j takes its column of U from orthogonality, and a zero C gives U = V = I.
-template <int D>
-__host__ __device__ __forceinline__ void pa_svd(const double (&C)[D][D], double (&U)[D][D], double (&sg)[D],
-                                                double (&V)[D][D]) {
-  static_assert(D == 2 || D == 3, "closed completion of U for d = 2, 3");
-  double A[D][D];
-#pragma unroll
-  for (int r = 0; r < D; ++r)
-#pragma unroll
-    for (int c = 0; c < D; ++c) A[r][c] = C[r][c];
-  pa_one_sided_jacobi<D>(A, V);
-#pragma unroll
-  for (int c = 0; c < D; ++c) {
-    double q = 0.0;
-#pragma unroll
-    for (int r = 0; r < D; ++r) q += A[r][c] * A[r][c];
-    sg[c] = sqrt(q);
-  }
-  pa_swap_cols<D>(A, V, sg, 0, 1);
-  if constexpr (D == 3) {
-    pa_swap_cols<D>(A, V, sg, 1, 2);
-    pa_swap_cols<D>(A, V, sg, 0, 1);
-  }
-  if (!(sg[0] > 0.0)) {  // C == 0: no rotation happened, V = I and so is U
-#pragma unroll
-    for (int r = 0; r < D; ++r)
-#pragma unroll
-      for (int c = 0; c < D; ++c) U[r][c] = V[r][c];
-    return;
-  }
-  const double detV = pa_det<D>(V);
-  double u0[D];
-#pragma unroll
-  for (int r = 0; r < D; ++r) u0[r] = A[r][0] / sg[0];
-  if constexpr (D == 2) {
-    // the last column is the perpendicular of the first, on the side of A's column (det U V^T = +1 when that is nil)
-    double u1[2] = {-u0[1], u0[0]};
-    const double side = u1[0] * A[0][1] + u1[1] * A[1][1];
-    const bool flip = sg[1] > kSvdNegligible * sg[0] ? side < 0.0 : detV < 0.0;
-    const double f = flip ? -1.0 : 1.0;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      U[r][0] = u0[r];
-      U[r][1] = f * u1[r];
-    }
-  } else {
-    double u1[3];
-    if (sg[1] > kSvdNegligible * sg[0]) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) u1[r] = A[r][1] / sg[1];
-    } else {  // any unit vector perpendicular to u0: u0 x (the axis u0 leans on least)
-      const double a0 = fabs(u0[0]), a1 = fabs(u0[1]), a2 = fabs(u0[2]);
-      const bool k0 = a0 <= a1 && a0 <= a2, k1 = !k0 && a1 <= a2;
-      const double e[3] = {k0 ? 1.0 : 0.0, k1 ? 1.0 : 0.0, (k0 || k1) ? 0.0 : 1.0};
-      u1[0] = u0[1] * e[2] - u0[2] * e[1];
-      u1[1] = u0[2] * e[0] - u0[0] * e[2];
-      u1[2] = u0[0] * e[1] - u0[1] * e[0];
-      const double nrm = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-#pragma unroll
-      for (int r = 0; r < 3; ++r) u1[r] /= nrm;
-    }
-    // the last column is +-(u0 x u1): Jacobi left A's columns orthogonal to rounding, so this IS a_2 / sigma_2 where
-    // that is meaningful, and stays a unit vector where it is not
-    double u2[3] = {u0[1] * u1[2] - u0[2] * u1[1], u0[2] * u1[0] - u0[0] * u1[2], u0[0] * u1[1] - u0[1] * u1[0]};
-    const double side = u2[0] * A[0][2] + u2[1] * A[1][2] + u2[2] * A[2][2];
-    const bool flip = (sg[1] > kSvdNegligible * sg[0] && sg[2] > kSvdNegligible * sg[0]) ? side < 0.0 : detV < 0.0;
-    const double f = flip ? -1.0 : 1.0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      U[r][0] = u0[r];
-      U[r][1] = u1[r];
-      U[r][2] = f * u2[r];
-    }
-  }
-}
-
-// Reduced raw moments (about the pivots px, py) -> R (d x d), T (d), s, singular values of C; all fp64.
-template <int D>
-__host__ __device__ __forceinline__ void pa_solve(const double* mom, const double (&px)[D], const double (&py)[D],
-                                                  bool estimate_scale, bool allow_reflection, double eps,
-                                                  double (&R)[D][D], double (&T)[D], double& s, double (&sg)[D]) {
-  using S = PaSlot<D>;
-  const double W = mom[S::kSw] > eps ? mom[S::kSw] : eps;
-  const double sw2 = mom[S::kSw2];
-  double xm[D], ym[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    xm[d] = mom[S::kSwx + d] / W;
-    ym[d] = mom[S::kSwy + d] / W;
-  }
-  double C[D][D];
-  double xcov = mom[S::kSxx];
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    xcov += xm[a] * (sw2 * xm[a] - 2.0 * mom[S::kSw2x + a]);
-#pragma unroll
-    for (int b = 0; b < D; ++b)
-      C[a][b] = (mom[S::kSxy + a * D + b] - xm[a] * mom[S::kSw2y + b] - mom[S::kSw2x + a] * ym[b] +
-                 sw2 * xm[a] * ym[b]) / W;
-  }
-  xcov /= W;
-  double U[D][D], V[D][D];
-  pa_svd<D>(C, U, sg, V);
-  const double e = allow_reflection ? 1.0 : (pa_det<D>(U) * pa_det<D>(V) < 0.0 ? -1.0 : 1.0);
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double r = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) r += (k == D - 1 ? e : 1.0) * U[a][k] * V[b][k];
-      R[a][b] = r;
-    }
-  s = 1.0;
-  if (estimate_scale) {
-    double tr = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) tr += (k == D - 1 ? e : 1.0) * sg[k];
-    s = tr / (xcov > eps ? xcov : eps);
-  }
-#pragma unroll
-  for (int b = 0; b < D; ++b) {
-    double xr = 0.0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) xr += (px[a] + xm[a]) * R[a][b];
-    T[b] = (py[b] + ym[b]) - s * xr;
-  }
 }
 
 template <int D>
