@@ -154,12 +154,14 @@ int grid_refine(const KnnArgs& a, const GridWs& ws) {
   const int64_t per_cloud = 256 / (a.N > 0 ? a.N : 1);
   const dim3 grid((unsigned)(per_cloud < kRefineWgs ? kRefineWgs : (per_cloud > 64 ? 64 : per_cloud)), (unsigned)a.N);
   const int rc = with_exact<3>(Ints<1, 2, 3>{}, a.D, [&](auto D) {
-    static bool attr = false;  // per instance
-    if (!attr) {
+    static bool attr[64] = {false};  // per instance and DEVICE (a process may drive several GPUs, as in fps_num_cus)
+    int dev = -1;
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;  // (unknown: set it on every call)
+    if (!known || !attr[dev]) {
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(grid_refine_build_kernel<D>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return check_launch("grid refine attribute");
-      attr = true;
+      if (known) attr[dev] = true;
     }
     hipLaunchKernelGGL((grid_refine_build_kernel<D>), grid, dim3(kRefineBlock), lds, a.stream, ws, a.P2);
     return POINTOPS_OK;

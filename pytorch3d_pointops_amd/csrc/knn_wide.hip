@@ -255,12 +255,14 @@ constexpr size_t kWideLdsMax = 160 * 1024;
 template <int KC, int NORM, int WG>
 static int launch_wide(const KnnArgs& a, size_t lds, int S, void* workspace) {
   auto kern = knn_wide_kernel<KC, NORM, WG>;
-  static bool attr_set = false;  // per instantiation
-  if (!attr_set) {
+  static bool attr_set[64] = {false};  // per instantiation and DEVICE (a process may drive several GPUs)
+  int dev = -1;
+  const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;  // (unknown: set it on every call)
+  if (!known || !attr_set[dev]) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)kWideLdsMax) != hipSuccess)
       return check_launch("knn_points_idx(wide attribute)");
-    attr_set = true;
+    if (known) attr_set[dev] = true;
   }
   const int tiles = (int)ceil_div(a.P1, WG);
   if (a.N * tiles >= (1LL << 31)) return POINTOPS_EINVAL;

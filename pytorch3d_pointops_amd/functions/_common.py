@@ -10,16 +10,31 @@ from typing import Optional, Tuple
 import torch
 
 _LENGTHS_CACHE = {}
+# hipStream_t (as an int) of torch's current stream on a device: one C call where torch has it
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or \
+    (lambda index: torch.cuda.current_stream(index).cuda_stream)
 
 
 def full_lengths(n: int, p: int, device) -> torch.Tensor:
     """(n,) int64 tensor filled with p -- the default `lengths` (reference: functions/knn.py:184-187).
-    The kernels only read it, so one tensor per (n, p, device) is kept and reused: it saves a fill launch per
-    call, and passing the SAME tensor for both point sets lets the C ABI recognise a self-query (p1 is p2)."""
-    key = (int(n), int(p), str(device))
+    The kernels only read it, so one tensor per (n, p, device, current stream of that device) is kept and reused: it
+    saves a fill launch per call, and passing the SAME tensor for both point sets lets the C ABI recognise a
+    self-query (p1 is p2).
+
+    The STREAM is part of the key because the fill is a launch on the stream that is current at first use: a call on
+    another stream has no ordering against it (it would read the tensor before it is written), and dropping the entry
+    hands its block back to the allocator, which orders the next user behind the launches of the ALLOCATING stream
+    only.  With one tensor per stream every reader is behind the fill by stream order, and an evicted block is reused
+    behind the only launches that read it; no call ever synchronises.  Nothing made during a HIP-graph capture is kept:
+    such a tensor lives in the graph's private pool and is filled by a replay, not now."""
+    if torch.compiler.is_compiling():  # a tensor of the traced graph (the stream of the key cannot be traced)
+        return torch.full((n,), p, dtype=torch.int64, device=device)
+    on_gpu = device.type == "cuda"  # (a CPU tensor gets its lengths too: the GPU-only error is the native wrappers')
+    index = (device.index if device.index is not None else torch.cuda.current_device()) if on_gpu else -1
+    key = (int(n), int(p), index, _raw_stream(index) if on_gpu else 0)
     t = _LENGTHS_CACHE.get(key)
     if t is None:
-        if torch.compiler.is_compiling():  # a tensor of the traced graph: the cache holds real tensors only
+        if on_gpu and torch.cuda.is_current_stream_capturing():  # the cache holds real, filled tensors only
             return torch.full((n,), p, dtype=torch.int64, device=device)
         if len(_LENGTHS_CACHE) > 64:
             _LENGTHS_CACHE.clear()

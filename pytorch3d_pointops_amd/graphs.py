@@ -11,10 +11,12 @@ it with one `hipGraphLaunch`.
 Every operator of the package can be captured because the C ABI never synchronises, never allocates and takes every
 data-dependent decision (grid or scan per cloud, which fallback pass a query needs) ON THE DEVICE; the chamfer's
 reverse search forks to its side stream and joins back through events, which a capture follows.  The host side keeps
-two promises while `torch.cuda.is_current_stream_capturing()`: the opt-in grid reuse is bypassed (a captured reuse
-level would be replayed blindly), and the lengths validation's device-to-host read has happened during the warm-up
-calls (`_common.lengths_max` remembers it).  Workspaces are allocated per call, so under capture they come from the
-graph's private pool like every other tensor of the captured calls.
+three promises while `torch.cuda.is_current_stream_capturing()`: the opt-in grid reuse is bypassed (a captured reuse
+level would be replayed blindly), the lengths validation's device-to-host read has happened during the warm-up
+calls (`_common.lengths_max` remembers it), and a default `lengths` tensor made under capture is not cached (it lives
+in the graph's pool and is filled by a replay; `capture` warms up on its capture stream, so its calls find the
+tensors the warm-up cached for that stream and the graph holds no fill).  Workspaces are allocated per call, so under
+capture they come from the graph's private pool like every other tensor of the captured calls.
 
     step = capture(lambda x, y: chamfer_distance(x, y)[0], (x, y), backward=True)
     loss, (gx, gy) = step(new_x, new_y)      # copies into the static inputs, replays, returns the static results
@@ -57,7 +59,9 @@ class GraphedCall:
         dev = inputs[0].device
         with torch.cuda.device(dev):
             # warm-up on a side stream (torch's capture protocol): first-use work -- the library's side stream and
-            # events, kernel attributes, cached default lengths, the lengths validation -- happens here, not under capture
+            # events, kernel attributes, cached default lengths, the lengths validation -- happens here, not under
+            # capture.  The capture runs on the SAME stream: the default lengths are cached per stream, so the captured
+            # calls find the tensors the warm-up filled instead of adding a fill to every replay.
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -65,9 +69,10 @@ class GraphedCall:
                     run()
             torch.cuda.current_stream().wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with torch.cuda.graph(self.graph, stream=side):
                 self.outputs, self._single, self.grads = run()
-        # tensors the captured launches may point at although no Python object of the capture owns them
+        # tensors the captured launches may point at although no Python object of the capture owns them: the cached
+        # default lengths (filled on `side` before the capture began; the cache may drop them later)
         from .functions import _common
         self._keepalive = list(_common._LENGTHS_CACHE.values())
 

@@ -634,8 +634,10 @@ def test_host_caches_across_tracing(dev):
     assert all(torch.equal(u, v) for u, v in zip(got, want))
     again = fn(a, b)  # eager with the same (n, p)
     assert all(torch.equal(u, v) for u, v in zip(again, want))
-    for (n, p, _), t in _common._LENGTHS_CACHE.items():
+    assert _common._LENGTHS_CACHE  # (the eager call above cached its default lengths: the loop below is not empty)
+    for (n, p, index, _), t in _common._LENGTHS_CACHE.items():  # key: (n, p, device index, stream)
         assert type(t) is torch.Tensor and t.device == a.device and t.shape == (n,) and bool((t == p).all())
+        assert index == a.device.index
     a2, b2 = a[:2, :40].contiguous(), b[:2, :77].contiguous()  # compiled again at another shape
     assert all(torch.equal(u, v) for u, v in zip(compiled(a2, b2), fn(a2, b2)))
     assert all(torch.equal(u, v) for u, v in zip(fn(a2, b2), knn_points(a2, b2, G(np.array([40, 40]), dev),
