@@ -137,7 +137,16 @@ __device__ __forceinline__ void lane_walk(const char* __restrict__ spb, const un
       ii[u - u0] = __float_as_int(c[u].w);
     }
     // the reloads stay BEHIND the distances (hoisted above them, old and new records overlap in lifetime
-    // and the compiler copies four float4 per part to rotate the registers)
+    // and the compiler copies four float4 per part to rotate the registers).  The barrier alone pins the loads, not the
+    // distances: the compiler sank those below the reloads into the `valid` branches and kept the old records alive in
+    // copies (six v_mov_b64 + five v_mov_b32 per group of the queue kernels, behind s_waitcnt vmcnt(2) / (1) / (0));
+    // naming dd / ii as outputs of an empty asm ahead of the barrier makes them exist in registers here, and the group
+    // compiles to one vmcnt(0), the straight distances, the four gathers, the tests (profiles/lane_diet_resources.txt).
+    // (Queue kernels only: the direct-insert kernels were no faster with it, K = 1 a little slower.)
+    if constexpr (kUseQueue) {
+#pragma unroll
+      for (int t = 0; t < kSub; ++t) asm volatile("" : "+v"(dd[t]), "+v"(ii[t]));
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = u0; u < u0 + kSub; ++u) c[u] = record(off, u);  // next group's records into the same registers

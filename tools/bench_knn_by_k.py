@@ -16,7 +16,7 @@ def main():
     p1 = torch.from_numpy(synth.uniform_f32(11, (B, P, 3))).to(dev)
     p2 = torch.from_numpy(synth.uniform_f32(12, (B, P, 3))).to(dev)
     L = torch.full((B,), P, dtype=torch.int64, device=dev)
-    for K in (1, 2, 4, 8, 16, 32):
+    for K in (1, 2, 4, 8, 16, 32, 64):
         for _ in range(3):
             _C.knn_points_idx(p1, p2, L, L, 2, K, -1)
         times = []
