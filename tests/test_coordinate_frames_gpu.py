@@ -434,8 +434,8 @@ def _fps_base(name):
 
 
 _FPS = {
-    "fps_small": (_fps_base, ["per_cloud_k", "lattice_ties"]),  # P <= 4096: fps_small_kernel (fps.hip)
-    "fps_clusters": (_fps_base, ["start_nonzero", "lattice_ties"]),  # fps_small=0: the 16-wave cluster kernel
+    "fps_small": (_fps_base, ["per_cloud_k", "lattice_ties"]),  # P <= 4096: fps_single_kernel<.., 256> (fps.hip)
+    "fps_clusters": (_fps_base, ["start_nonzero", "lattice_ties"]),  # fps_small=0: fps_single_kernel<.., 1024>
     "fps_multi_workgroup": (_fps_base, ["multi_10000", "multi_40000", "multi_9000_d2"]),  # P > 4096: clusters of workgroups
 }
 

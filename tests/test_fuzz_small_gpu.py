@@ -1,6 +1,6 @@
-"""Randomised parity soak of the small-batch kernels (knn_small.hip, ball_small.hip, fps_small_kernel) and of the paths
-they replaced, against the CPU oracle: random batch sizes, ragged lengths (zeros included), D, K, norms, lattices for
-ties.  Every kernel choice a knob can force is run on every case and must reproduce the oracle bit for bit."""
+"""Randomised parity soak of the small-batch kernels (knn_small.hip, ball_small.hip, fps_single_kernel<.., 256>) and of
+the paths they replaced, against the CPU oracle: random batch sizes, ragged lengths (zeros included), D, K, norms,
+lattices for ties.  Every kernel choice a knob can force is run on every case and must reproduce the oracle bit for bit."""
 import numpy as np
 import pytest
 import torch

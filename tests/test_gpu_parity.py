@@ -555,8 +555,9 @@ def test_ball_query_tile_scan_sinks_agree(dev, oracle, monkeypatch, D):
 @pytest.mark.parametrize("kernel", ["auto", "clusters"])
 @pytest.mark.parametrize("name", sorted(cases.fps_cases()))
 def test_sample_farthest_points(dev, oracle, monkeypatch, name, kernel):
-    """Reference goldens + oracle; "auto": clouds of up to 4096 points take the four-wave kernel (fps_small_kernel),
-    "clusters": the 16-wave cluster kernel they took before (POINTOPS_DEBUG fps_small=0)."""
+    """Reference goldens + oracle; "auto": clouds of up to 4096 points take the four-wave kernel
+    (fps_single_kernel<.., 256>), "clusters": the 16-wave one they took before, today fps_single_kernel<.., 1024>
+    (POINTOPS_DEBUG fps_small=0)."""
     from pytorch3d_pointops_amd import _C
 
     if kernel == "clusters":
