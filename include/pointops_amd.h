@@ -157,7 +157,8 @@ int pointops_sample_farthest_points(const float* points, const int64_t* lengths,
  *  packed_to_padded_tensor_cpu.cpp:11-70).
  *   packed (F,D), first_idxs (B,), padded (B,max_size,D); cloud b owns packed rows
  *   [first_idxs[b], first_idxs[b+1]) (last cloud: F).  Padding is zero-filled; packed
- *   rows owned by no cloud are zero.
+ *   rows owned by no cloud are zero.  Any B < 2^31, like the reference (65536 clouds and
+ *   more run as several launches of 65535 clouds).
  */
 int pointops_packed_to_padded(const float* packed, const int64_t* first_idxs, int64_t F,
                               int64_t B, int64_t max_size, int64_t D, float* padded,
@@ -223,6 +224,8 @@ int pointops_chamfer_reduce(const float* dists, const int64_t* lengths, const fl
  * x_feats / y_feats / C are HOST arrays of F (<= 4) device pointers / channel counts (<= 16).
  * The backward is closed-form: grad_x, grad_x_feats written densely, grad_y / grad_y_feats are
  * zero-filled then scatter-added with fp32 atomics.  grad_out is (1+F, N).
+ * Any N < 2^31 in every chamfer entry, the pair entries below included (65536 clouds and more run as several launches
+ * of 65535 clouds over the same buffers; the workspace sizes are those of the whole batch).
  */
 size_t pointops_chamfer_workspace_bytes(int64_t N, int64_t P1);
 int pointops_chamfer_forward(const float* dists, const int64_t* idx, const int64_t* x_lengths,
@@ -310,7 +313,8 @@ int pointops_point_covariances_backward(const float* knn, const float* grad_cov,
  *   disambiguate != 0: columns 0 (n) and 2 (z) are negated when fewer than K/2 neighbours have (x_k - x_i).v > 0
  *   (x_i = points[n,i]), and column 1 becomes n x z.  Otherwise the eigenvector signs are implementation-defined.
  *   Rows i >= lengths[n] are zero in both outputs; a zero C gives zero curvatures and the identity frame (before
- *   disambiguation).  No atomics (deterministic), no workspace.  N < 65536.
+ *   disambiguation).  No atomics (deterministic), no workspace.  N < 65536 (a bigger batch is POINTOPS_EINVAL:
+ *   nothing is launched, no output is written); the backward below has no such limit.
  * Backward: grad_cov (N,P,3,3) from the saved outputs and their gradients (N,P,3), (N,P,3,3) -- with disambiguate,
  *   y = n x z is folded into n and z first; then grad_C = sum_i g_i v_i v_i^T
  *   + sum_{i != j} (v_j . grad_v_i) / (lambda_i - lambda_j) v_j v_i^T.  Rows i >= lengths[n] get 0.  Coincident
@@ -337,6 +341,8 @@ int pointops_local_frames_backward(const float* curvatures, const float* frames,
  *   orthogonal R, the identity for C == 0.
  *   moments (N, 3+4D+D*D) fp64 or NULL: the reduced sums about the pivots X[n,0], Y[n,0] (what the backward needs);
  *   singular_values (N,D) fp32 or NULL: S, descending.  workspace: pointops_points_alignment_workspace_bytes(N,P,D).
+ *   N < 65536 in both entries (the cloud is a grid's y coordinate); a bigger batch is POINTOPS_EINVAL, nothing is
+ *   launched and no output is written.
  * Backward (without idx): grad_moments (N, 3+4D+D*D) fp64 -> grad_X, grad_Y (N,P,D), grad_weights (N,P) or NULL;
  *   rows i >= lengths[n] get 0.  The gradient of the moments is the host's business (N tiny solves).
  */
@@ -362,6 +368,7 @@ int pointops_points_alignment_backward(const float* X, const float* Y, const int
  *   previous call into knn_workspace (see pointops_knn_points_idx_reuse); -1 = no search, idx (N,P1) is an input.
  *   idx (N,P1) int64 and dists (N,P1) fp32 are outputs of the search; R, T, s as above.  N, P1, P2 >= 1.
  *   workspace: pointops_icp_workspace_bytes(N, P1, D).  Nothing synchronises; no floating-point atomics.
+ *   N < 65536, as for pointops_points_alignment.
  */
 size_t pointops_icp_workspace_bytes(int64_t N, int64_t P1, int64_t D);
 int pointops_icp_iteration(const float* X_init, float* Xt, const float* Y, const int64_t* lengths_x,
@@ -376,7 +383,8 @@ int pointops_icp_iteration(const float* X_init, float* Xt, const float* Y, const
  * under them, in two fused passes over a neighbour table -- device half of functions/fpfh.py.  The semantics are this
  * library's own; all arithmetic is unfused fp32 in the order written.
  *   points (N,P,3), normals (N,P,3) fp32 (used as given, never renormalised); idx (N,P,K) int64: the knn_points or
- *   ball_query table of the cloud against itself; lengths (N,) or NULL (= P).  1 <= K <= 255, N < 65536.
+ *   ball_query table of the cloud against itself; lengths (N,) or NULL (= P).  1 <= K <= 255, N < 65536 in both entries (a
+ *   bigger batch is POINTOPS_EINVAL: nothing is launched, no output is written).
  *   Live slots: slot k of row i < lengths[n] is live when j = idx[n,i,k] has 0 <= j < lengths[n], j != i and
  *   d2 = dp.dp > 0 for dp = p_j - p_i (ball_query's -1 padding, the self match and exact duplicates are dead).
  *   Pair features of a live slot: d = sqrtf(d2), a1 = n_i.dp / d, a2 = n_j.dp / d.  If |a1| < |a2|: ns = n_j,

@@ -547,6 +547,23 @@ def alignment_moment_count(D: int) -> int:
     return 3 + 4 * D + D * D
 
 
+# The alignment entries take N < 65536 clouds (include/pointops_amd.h): a bigger batch goes to them in slices of this
+# many clouds, each a contiguous view of the inputs and of the outputs, one after the other through one workspace.
+ALIGNMENT_MAX_CLOUDS = 65535
+
+
+def _cloud_slices(N: int):
+    """[(slice or None, clouds)]: None = the whole batch as it is (no views made on the usual, host-bound path)."""
+    if N <= ALIGNMENT_MAX_CLOUDS:
+        return [(None, N)]
+    return [(slice(a, min(a + ALIGNMENT_MAX_CLOUDS, N)), min(ALIGNMENT_MAX_CLOUDS, N - a))
+            for a in range(0, N, ALIGNMENT_MAX_CLOUDS)]
+
+
+def _rows(t, sl):
+    return t if t is None or sl is None else t[sl]
+
+
 def points_alignment(X, Y, idx, lengths, weights, estimate_scale: bool, allow_reflection: bool, eps: float,
                      want_moments: bool = False):
     """X (N,P,D), Y (N,P2,D) fp32, idx (N,P) int64 or None (row i of X <-> Y[n, idx[n,i]]; None: Y[n,i]), lengths
@@ -569,9 +586,12 @@ def points_alignment(X, Y, idx, lengths, weights, estimate_scale: bool, allow_re
     s = _out((N,), dtype=torch.float32, device=dev)
     sing = _out((N, D), dtype=torch.float32, device=dev)
     moments = _out((N, alignment_moment_count(D)), dtype=torch.float64, device=dev) if want_moments else None
-    _call.points_alignment("points_alignment", dev, X, Y, idx, lengths, weights, N, P, P2, D, bool(estimate_scale),
-                           bool(allow_reflection), float(eps), R, T, s, moments, sing,
-                           *_scratch(dev, _lib.pointops_points_alignment_workspace_bytes, N, P, D))
+    scratch = _scratch(dev, _lib.pointops_points_alignment_workspace_bytes, min(N, ALIGNMENT_MAX_CLOUDS), P, D)
+    for sl, n in _cloud_slices(N):
+        _call.points_alignment("points_alignment", dev, _rows(X, sl), _rows(Y, sl), _rows(idx, sl), _rows(lengths, sl),
+                               _rows(weights, sl), n, P, P2, D, bool(estimate_scale), bool(allow_reflection),
+                               float(eps), _rows(R, sl), _rows(T, sl), _rows(s, sl), _rows(moments, sl),
+                               _rows(sing, sl), *scratch)
     return R, T, s, sing, moments
 
 
@@ -587,8 +607,10 @@ def points_alignment_backward(X, Y, lengths, weights, grad_moments):
     grad_moments = grad_moments.contiguous()
     grad_X, grad_Y = _out_like(X), _out_like(Y)
     grad_w = _out_like(weights) if weights is not None else None
-    _call.points_alignment_backward("points_alignment_backward", dev, X, Y, lengths, weights, grad_moments, N, P, D,
-                                    grad_X, grad_Y, grad_w)
+    for sl, n in _cloud_slices(N):
+        _call.points_alignment_backward("points_alignment_backward", dev, _rows(X, sl), _rows(Y, sl),
+                                        _rows(lengths, sl), _rows(weights, sl), _rows(grad_moments, sl), n, P, D,
+                                        _rows(grad_X, sl), _rows(grad_Y, sl), _rows(grad_w, sl))
     return grad_X, grad_Y, grad_w
 
 

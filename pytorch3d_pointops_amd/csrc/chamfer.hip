@@ -355,6 +355,25 @@ __global__ __launch_bounds__(kCfBlock) void chamfer_backward4_kernel(
 // workgroups per cloud of chamfer_forward_kernel, one partial sum per term each (an empty cloud still takes one)
 static int cf_chunks(int64_t P1) { return (int)ceil_div(P1 > 0 ? P1 : 1, (int64_t)kCfBlock * kCfPerThread); }
 
+// clouds per launch of the kernels that read the cloud from blockIdx.y (at most 65535).  A bigger batch runs in slices
+// of this many clouds: every per-cloud pointer is advanced to the slice's first cloud (cf_slice), the kernels are the
+// same, and a batch below 65536 is one launch with the pointers as given.  Arrays laid out (1+F, N) keep N as their
+// row stride and are advanced by the cloud alone.
+constexpr int64_t kCfBatchSlice = 65535;
+
+// the feature pointers of the slice starting at cloud n0 (x side P1 rows per cloud, y side P2)
+static ChamferFeat cf_slice(const ChamferFeat& ft, int64_t n0, int64_t P1, int64_t P2) {
+  ChamferFeat s = ft;
+  for (int f = 0; f < ft.F; ++f) {
+    const int64_t ox = n0 * P1 * ft.C[f], oy = n0 * P2 * ft.C[f];
+    s.x[f] = ft.x[f] + ox;
+    s.y[f] = ft.y[f] + oy;
+    s.gx[f] = ft.gx[f] ? ft.gx[f] + ox : nullptr;
+    s.gy[f] = ft.gy[f] ? ft.gy[f] + oy : nullptr;
+  }
+  return s;
+}
+
 }  // namespace pointops
 
 extern "C" size_t pointops_chamfer_workspace_bytes(int64_t N, int64_t P1) {
@@ -384,7 +403,7 @@ extern "C" int pointops_chamfer_forward(const float* dists, const int64_t* idx, 
                                         const float* const* y_feats, const int64_t* C, int abs_cosine, int mean,
                                         float* out, void* workspace, size_t workspace_bytes, void* stream_) {
   using namespace pointops;
-  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && N < 65536, "chamfer_forward: bad sizes");
+  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && N < (1LL << 31), "chamfer_forward: bad sizes");
   if (N == 0) return POINTOPS_OK;
   ChamferFeat ft;
   const int rc = cf_fill(&ft, F, x_feats, y_feats, nullptr, nullptr, C);
@@ -393,8 +412,14 @@ extern "C" int pointops_chamfer_forward(const float* dists, const int64_t* idx, 
                              "chamfer_forward: workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   const int chunks = cf_chunks(P1);
-  hipLaunchKernelGGL(chamfer_forward_kernel, dim3((unsigned)chunks, (unsigned)N), dim3(kCfBlock), 0, stream, dists,
-                     idx, x_lengths, y_lengths, P1, P2, ft, abs_cosine, chunks, (float*)workspace);
+  for (int64_t n0 = 0; n0 < N; n0 += kCfBatchSlice) {
+    const int64_t nn = N - n0 < kCfBatchSlice ? N - n0 : kCfBatchSlice;
+    hipLaunchKernelGGL(chamfer_forward_kernel, dim3((unsigned)chunks, (unsigned)nn), dim3(kCfBlock), 0, stream,
+                       dists + n0 * P1, idx + n0 * P1, x_lengths + n0, y_lengths + n0, P1, P2,
+                       n0 ? cf_slice(ft, n0, P1, P2) : ft, abs_cosine, chunks,
+                       (float*)workspace + n0 * chunks * (1 + kCfMaxFeat));
+  }
+  // (the cloud is blockIdx.x here: any N below 2^31 in one launch)
   hipLaunchKernelGGL(chamfer_finalize_kernel, dim3((unsigned)N), dim3(kWave), 0, stream, (const float*)workspace,
                      x_lengths, weights, (int)N, chunks, F, mean, out);
   return check_launch("chamfer_forward");
@@ -408,7 +433,7 @@ static int chamfer_backward_impl(const float* x, const float* y, const int64_t* 
                                  float* const* grad_y_feats, void* stream_, int acc) {
   using namespace pointops;
   POINTOPS_REQUIRE(norm == 1 || norm == 2, "chamfer_backward: norm must be 1 or 2");
-  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && D >= 1 && N < 65536, "chamfer_backward: bad sizes");
+  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && D >= 1 && N < (1LL << 31), "chamfer_backward: bad sizes");
   ChamferFeat ft;
   const int rc = cf_fill(&ft, F, x_feats, y_feats, grad_x_feats, grad_y_feats, C);
   if (rc != POINTOPS_OK) return rc;
@@ -422,19 +447,27 @@ static int chamfer_backward_impl(const float* x, const float* y, const int64_t* 
   if (N == 0 || P1 == 0) return POINTOPS_OK;
   bool four = D <= 4;
   for (int f = 0; f < F; ++f) four = four && C[f] <= 4;
-  if (four) {
-    const dim3 grid4((unsigned)ceil_div(P1 * 4, kCfBlock), (unsigned)N), block4(kCfBlock);
-    with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
-      hipLaunchKernelGGL(chamfer_backward4_kernel<NORM>, grid4, block4, 0, stream, x, y, idx, x_lengths, y_lengths,
-                         weights, grad_out, (int)N, P1, P2, (int)D, ft, abs_cosine, mean, acc, grad_x, grad_y);
-    });
-    return check_launch("chamfer_backward");
+  // slices of kCfBatchSlice clouds: grad_out is (1+F, N) and keeps its stride N, everything else moves by whole clouds
+  for (int64_t n0 = 0; n0 < N; n0 += kCfBatchSlice) {
+    const unsigned nn = (unsigned)(N - n0 < kCfBatchSlice ? N - n0 : kCfBatchSlice);
+    const ChamferFeat fs = n0 ? cf_slice(ft, n0, P1, P2) : ft;
+    const float *xs = x + n0 * P1 * D, *ys = y + n0 * P2 * D, *ws = weights ? weights + n0 : nullptr;
+    const int64_t *is = idx + n0 * P1, *xl = x_lengths + n0, *yl = y_lengths + n0;
+    float *gxs = grad_x + n0 * P1 * D, *gys = grad_y + n0 * P2 * D;
+    if (four) {
+      const dim3 grid4((unsigned)ceil_div(P1 * 4, kCfBlock), nn), block4(kCfBlock);
+      with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+        hipLaunchKernelGGL(chamfer_backward4_kernel<NORM>, grid4, block4, 0, stream, xs, ys, is, xl, yl, ws,
+                           grad_out + n0, (int)N, P1, P2, (int)D, fs, abs_cosine, mean, acc, gxs, gys);
+      });
+    } else {
+      const dim3 grid((unsigned)ceil_div(P1, kCfBlock), nn), block(kCfBlock);
+      with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
+        hipLaunchKernelGGL(chamfer_backward_kernel<NORM>, grid, block, 0, stream, xs, ys, is, xl, yl, ws,
+                           grad_out + n0, (int)N, P1, P2, (int)D, fs, abs_cosine, mean, acc, gxs, gys);
+      });
+    }
   }
-  const dim3 grid((unsigned)ceil_div(P1, kCfBlock), (unsigned)N), block(kCfBlock);
-  with_exact<2>(Ints<1, 2>{}, norm, [&](auto NORM) {
-    hipLaunchKernelGGL(chamfer_backward_kernel<NORM>, grid, block, 0, stream, x, y, idx, x_lengths, y_lengths, weights,
-                       grad_out, (int)N, P1, P2, (int)D, ft, abs_cosine, mean, acc, grad_x, grad_y);
-  });
   return check_launch("chamfer_backward");
 }
 
@@ -577,7 +610,7 @@ extern "C" int pointops_chamfer_pair_forward(const float* x, const float* y, con
                                              float* const* outs, void* workspace, size_t workspace_bytes,
                                              void* stream_) {
   using namespace pointops;
-  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && D >= 1 && N < 65536 && F >= 0 && F <= kCfMaxFeat,
+  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && D >= 1 && N < (1LL << 31) && F >= 0 && F <= kCfMaxFeat,
                    "chamfer_pair_forward: bad sizes");
   POINTOPS_REQUIRE(batch_reduction >= 0 && batch_reduction <= 2, "chamfer_pair_forward: batch_reduction must be 0, 1 or 2");
   // (N = 0 runs through: the searches and reductions return at once, the combine writes 0 after a batch reduction)
@@ -631,7 +664,7 @@ extern "C" int pointops_chamfer_pair_backward(const float* x, const float* y, co
                                               float* const* grad_y_feats, void* workspace, size_t workspace_bytes,
                                               void* stream_) {
   using namespace pointops;
-  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && D >= 1 && N < 65536 && F >= 0 && F <= kCfMaxFeat,
+  POINTOPS_REQUIRE(N >= 0 && P1 >= 0 && P2 >= 0 && D >= 1 && N < (1LL << 31) && F >= 0 && F <= kCfMaxFeat,
                    "chamfer_pair_backward: bad sizes");
   POINTOPS_REQUIRE(batch_reduction >= 0 && batch_reduction <= 2, "chamfer_pair_backward: batch_reduction must be 0, 1 or 2");
   if (N == 0) return POINTOPS_OK;

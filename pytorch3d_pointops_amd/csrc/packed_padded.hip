@@ -18,6 +18,10 @@ namespace pointops {
 
 constexpr int kPpBlock = 256;
 constexpr int kPpPerThread = 4;
+// clouds per launch: the cloud is blockIdx.y (at most 65535).  A bigger batch runs in slices of this many clouds, each
+// launch seeing first_idxs and the padded image from its first cloud on and the number of clouds from there to the END
+// of the batch (so that `b + 1 < B` still tells the last cloud of the batch); a batch below 65536 is one launch.
+constexpr int64_t kPpBatchSlice = 65535;
 
 __global__ __launch_bounds__(kPpBlock) void packed_to_padded_kernel(
     const float* __restrict__ packed, const int64_t* __restrict__ first_idxs, int64_t F, int B,
@@ -72,12 +76,16 @@ extern "C" int pointops_packed_to_padded(const float* packed, const int64_t* fir
                                          int64_t B, int64_t max_size, int64_t D, float* padded,
                                          void* stream_) {
   POINTOPS_REQUIRE(F >= 0 && B >= 0 && max_size >= 0 && D >= 1, "packed_to_padded: bad sizes");
-  POINTOPS_REQUIRE(B < 65536, "packed_to_padded: batch must be < 65536");
+  POINTOPS_REQUIRE(B < (1LL << 31), "packed_to_padded: batch must be < 2^31");
   if (B == 0 || max_size == 0) return POINTOPS_OK;
   const int64_t chunks = ceil_div(max_size * D, (int64_t)kPpBlock * kPpPerThread);
   POINTOPS_REQUIRE(chunks < (1LL << 31), "packed_to_padded: grid too large");
-  hipLaunchKernelGGL(packed_to_padded_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(kPpBlock), 0,
-                     (hipStream_t)stream_, packed, first_idxs, F, (int)B, max_size, D, padded);
+  for (int64_t b0 = 0; b0 < B; b0 += kPpBatchSlice) {
+    const int64_t nb = B - b0 < kPpBatchSlice ? B - b0 : kPpBatchSlice;
+    hipLaunchKernelGGL(packed_to_padded_kernel, dim3((unsigned)chunks, (unsigned)nb), dim3(kPpBlock), 0,
+                       (hipStream_t)stream_, packed, first_idxs + b0, F, (int)(B - b0), max_size, D,
+                       padded + b0 * max_size * D);
+  }
   return check_launch("packed_to_padded");
 }
 
@@ -85,7 +93,7 @@ extern "C" int pointops_padded_to_packed(const float* padded, const int64_t* fir
                                          int64_t B, int64_t max_size, int64_t D, float* packed,
                                          void* stream_) {
   POINTOPS_REQUIRE(F >= 0 && B >= 0 && max_size >= 0 && D >= 1, "padded_to_packed: bad sizes");
-  POINTOPS_REQUIRE(B < 65536, "padded_to_packed: batch must be < 65536");
+  POINTOPS_REQUIRE(B < (1LL << 31), "padded_to_packed: batch must be < 2^31");
   hipStream_t stream = (hipStream_t)stream_;
   if (F * D > 0) {
     // rows owned by no cloud stay zero (reference: at::zeros, ..._cpu.cpp:52-53)
@@ -95,7 +103,10 @@ extern "C" int pointops_padded_to_packed(const float* padded, const int64_t* fir
   if (B == 0 || max_size == 0 || F == 0) return POINTOPS_OK;
   const int64_t chunks = ceil_div(max_size * D, (int64_t)kPpBlock * kPpPerThread);
   POINTOPS_REQUIRE(chunks < (1LL << 31), "padded_to_packed: grid too large");
-  hipLaunchKernelGGL(padded_to_packed_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(kPpBlock), 0,
-                     stream, padded, first_idxs, F, (int)B, max_size, D, packed);
+  for (int64_t b0 = 0; b0 < B; b0 += kPpBatchSlice) {
+    const int64_t nb = B - b0 < kPpBatchSlice ? B - b0 : kPpBatchSlice;
+    hipLaunchKernelGGL(padded_to_packed_kernel, dim3((unsigned)chunks, (unsigned)nb), dim3(kPpBlock), 0, stream,
+                       padded + b0 * max_size * D, first_idxs + b0, F, (int)(B - b0), max_size, D, packed);
+  }
   return check_launch("padded_to_packed");
 }

@@ -290,12 +290,15 @@ __host__ __device__ __forceinline__ void pa_solve(const double* mom, const doubl
     for (int k = 0; k < D; ++k) tr += (k == D - 1 ? e : 1.0) * sg[k];
     s = tr / (xcov > eps ? xcov : eps);
   }
+  // the means about the origin: sum w x / W = px * (sum w / W) + xm.  The factor is exactly 1 unless W was clamped to
+  // eps -- a cloud whose weights are all zero (sum w = 0) has the means 0 and T = 0, whatever its row 0 holds
+  const double pw = mom[S::kSw] / W;
 #pragma unroll
   for (int b = 0; b < D; ++b) {
     double xr = 0.0;
 #pragma unroll
-    for (int a = 0; a < D; ++a) xr += (px[a] + xm[a]) * R[a][b];
-    T[b] = (py[b] + ym[b]) - s * xr;
+    for (int a = 0; a < D; ++a) xr += (px[a] * pw + xm[a]) * R[a][b];
+    T[b] = (py[b] * pw + ym[b]) - s * xr;
   }
 }
 

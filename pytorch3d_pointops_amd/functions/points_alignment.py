@@ -89,7 +89,8 @@ def _solve_from_moments(M, px, py, d: int, estimate_scale: bool, allow_reflectio
         s = (E * S).sum(1) / xcov.clamp(min=eps)
     else:
         s = torch.ones((N,), dtype=M.dtype, device=M.device)
-    T = (py + ym) - s[:, None] * torch.bmm((px + xm)[:, None, :], R)[:, 0]
+    pw = (Sw / W)[:, None]  # 1 unless W was clamped: the pivots count with the weight the cloud has (pa_solve)
+    T = (py * pw + ym) - s[:, None] * torch.bmm((px * pw + xm)[:, None, :], R)[:, 0]
     return R, T, s
 
 

@@ -143,6 +143,26 @@ def test_alignment_ragged_and_degenerate(dev):
     _check_alignment(got, ref.alignment(far, Yf), float(Yf.abs().max()), False, "far from the origin")
 
 
+def test_alignment_cloud_with_all_zero_weights(dev):
+    """A cloud whose rows hold points but whose weights are all zero (a mask that leaves nothing): by the definition
+    W = eps, the means and C are 0, so R = I and T = 0 exactly (s = 1, or 0 / eps = 0 with estimate_scale) -- the pivots (row 0 of X and of Y) must not leak
+    into T -- and the clouds next to it keep the bits they have without it."""
+    cpa = _api().corresponding_points_alignment
+    X = _cloud("uniform", 3, 50, 6400) + 0.5
+    Y = _moved(X, 6401)
+    w = torch.rand((3, 50), generator=_gen(6402)) + 0.1
+    w[1] = 0.0
+    for estimate_scale, allow_reflection in FLAGS:
+        got = cpa(X.to(dev), Y.to(dev), w.to(dev), estimate_scale, allow_reflection)
+        assert torch.equal(got.R[1].cpu(), torch.eye(3)) and torch.equal(got.T[1].cpu(), torch.zeros(3))
+        assert float(got.s[1]) == (0.0 if estimate_scale else 1.0)  # tr(E S) / max(0, eps) = 0
+        _check_alignment(got, ref.alignment(X, Y, w, estimate_scale, allow_reflection), float(Y.abs().max()),
+                         allow_reflection, f"zero weights {estimate_scale} {allow_reflection}")
+        alone = cpa(X[[0, 2]].to(dev), Y[[0, 2]].to(dev), w[[0, 2]].to(dev), estimate_scale, allow_reflection)
+        for u, v in zip(got, alone):
+            assert torch.equal(u[[0, 2]], v)
+
+
 def test_alignment_d2(dev):
     cpa = _api().corresponding_points_alignment
     g = _gen(8)
