@@ -12,6 +12,7 @@
 #include "debug.h"
 #include "grid.h"
 #include "knn_grid_search.h"
+#include "wave.h"
 
 namespace pointops {
 
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(kOrderScanBlock) void ball_order_scan_kernel(GridWs
   const int n = blockIdx.x;
   const GridCloud g = ws.cloud[n];
   if (g.use_grid || g.len2 <= 0) return;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = threadIdx.x;
   const int tiles = (g.len1 + 2047) / 2048;
   int* __restrict__ table = ws.order_table + (int64_t)n * tiles_cap * kOrderBins;
   constexpr int kPer = kOrderBins / kOrderScanBlock;  // consecutive cells per thread
@@ -288,17 +289,8 @@ __global__ __launch_bounds__(kOrderScanBlock) void ball_order_scan_kernel(GridWs
   // exclusive scan of the cell totals over the workgroup: list positions in cell order.  (Measured and dropped: the
   // cells whose balls the bounding box clips -- the long scans -- first in the list: 662 -> 776 us for the scan kernel.)
   __shared__ int s_tot[kOrderScanBlock / kWave];
-  const int mine = tot[0] + tot[1] + tot[2] + tot[3];
-  int inc = mine;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int v = __shfl_up(inc, off, kWave);
-    if (lane >= off) inc += v;
-  }
-  if (lane == kWave - 1) s_tot[wave] = inc;
-  __syncthreads();
-  int run = inc - mine;
-  for (int w = 0; w < wave; ++w) run += s_tot[w];
+  int total;
+  int run = block_exclusive_sum<kOrderScanBlock / kWave>(tot[0] + tot[1] + tot[2] + tot[3], s_tot, total);
   int start[kPer];
 #pragma unroll
   for (int u = 0; u < kPer; ++u) {

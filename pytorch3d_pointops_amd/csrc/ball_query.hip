@@ -27,6 +27,7 @@
 #include "debug.h"
 #include "knn_common.h"
 #include "knn_grid.h"
+#include "wave.h"
 
 namespace pointops {
 
@@ -68,14 +69,8 @@ __device__ __forceinline__ int ball_tile_scan(const float (&a)[DT], bool active,
   float blo[DT], bhi[DT];
 #pragma unroll
   for (int d = 0; d < DT; ++d) {
-    float mn = active ? a[d] : __builtin_inff(), mx = active ? a[d] : -__builtin_inff();
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-      mn = fminf(mn, __shfl_xor(mn, off, kWave));
-      mx = fmaxf(mx, __shfl_xor(mx, off, kWave));
-    }
-    blo[d] = mn;
-    bhi[d] = mx;
+    blo[d] = wave_min(active ? a[d] : __builtin_inff());
+    bhi[d] = wave_max(active ? a[d] : -__builtin_inff());
   }
   int count = 0;
   int j0 = 0;

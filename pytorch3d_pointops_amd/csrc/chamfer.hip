@@ -10,6 +10,7 @@
 #include "common.h"
 #include "debug.h"
 #include "knn_grid.h"
+#include "wave.h"
 #include "zero_fill.h"
 
 namespace pointops {
@@ -25,16 +26,13 @@ __global__ __launch_bounds__(kChBlock) void chamfer_reduce_kernel(
   const float* __restrict__ row = dists + (int64_t)n * P;
   float acc = 0.0f;
   for (int64_t i = threadIdx.x; i < len; i += kChBlock) acc += row[i];
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+  acc = wave_sum(acc);
   __shared__ float s[kChBlock / kWave];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   if (lane == 0) s[wave] = acc;
   __syncthreads();
   if (wave == 0) {
-    float v = lane < kChBlock / kWave ? s[lane] : 0.0f;
-#pragma unroll
-    for (int off = kChBlock / kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    float v = wave_sum<kChBlock / kWave>(lane < kChBlock / kWave ? s[lane] : 0.0f);
     if (lane == 0) {
       if (weights != nullptr) v *= weights[n];
       if (mean) v /= (float)(len < 1 ? 1 : len);
@@ -88,8 +86,7 @@ struct ChamferFeat {
 
 __device__ __forceinline__ float cf_block_sum(float v, float* s_red) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  v = wave_sum(v);
   if (lane == 0) s_red[wave] = v;
   __syncthreads();
   float t = 0.0f;
@@ -173,8 +170,7 @@ __global__ __launch_bounds__(kWave) void chamfer_finalize_kernel(const float* __
   for (int t = 0; t < 1 + F; ++t) {
     float v = 0.0f;
     for (int c = threadIdx.x; c < chunks; c += kWave) v += partial[((int64_t)n * chunks + c) * (1 + kCfMaxFeat) + t];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    v = wave_sum(v);
     if (threadIdx.x == 0) {
       if (weights != nullptr) v *= weights[n];
       if (mean) {
@@ -519,7 +515,7 @@ __global__ __launch_bounds__(kWave) void chamfer_pair_combine_kernel(const float
     acc += v;
   }
   if (reduce == 0) return;
-  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+  acc = wave_sum(acc);
   if (lane == 0) out[0] = reduce == 1 ? acc / (float)(N > 0 ? N : 1) : acc;
 }
 

@@ -172,6 +172,42 @@ __device__ __forceinline__ void point_cells(const GridCloud& g, float x, float y
   cy = cell_of(y, g.lo[1], g.inv_h, g.G[1]);
   cz = cell_of(z, g.lo[2], g.inv_h, g.G[2]);
 }
+// linear cell id: x fastest.  Every pass that bins a point goes through here, so they agree by construction.
+__device__ __forceinline__ int cell_index(const GridCloud& g, int cx, int cy, int cz) {
+  return (cz * g.G[1] + cy) * g.G[0] + cx;
+}
+__device__ __forceinline__ int cell_id(const GridCloud& g, float x, float y, float z) {
+  int cx, cy, cz;
+  point_cells(g, x, y, z, cx, cy, cz);
+  return cell_index(g, cx, cy, cz);
+}
+
+// a cloud's length as the kernels use it: inside [0, P]
+__device__ __forceinline__ int clamp_len(int64_t len, int P) {
+  const int l = (int)len;
+  return l < 0 ? 0 : (l > P ? P : l);
+}
+
+// fn(record, j, live) for the `count` records behind `src`, the BLOCK threads of the workgroup striding over them with
+// FOUR loads in flight each (a cell of 75 000 points is 73 strides of a 1024-thread workgroup: one load at a time made
+// every pass of grid_refine ~50 us).  Every thread makes the same number of trips and calls fn four times per trip --
+// past the end with live = false and a zero record -- so fn may exchange across the wave (wave_add of grid_build.hip).
+template <int BLOCK, typename Fn>
+__device__ __forceinline__ void for_each4(const float4* __restrict__ src, int count, Fn fn) {
+  for (int i0 = 0; i0 < count; i0 += 4 * BLOCK) {
+    float4 p[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = i0 + u * BLOCK + (int)threadIdx.x;
+      p[u] = j < count ? src[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = i0 + u * BLOCK + (int)threadIdx.x;
+      fn(p[u], j, j < count);
+    }
+  }
+}
 
 template <int NORM>
 __device__ __forceinline__ float face_bound(float t) {  // t = fl(|q - face|) >= 0

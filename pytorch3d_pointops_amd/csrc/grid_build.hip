@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "grid.h"
+#include "wave.h"
 
 namespace pointops {
 
@@ -26,6 +27,31 @@ constexpr int kCoarsePoints = 1024;  // entries a bin of the two-level sort aims
                                      // instead of 36 us)
 
 __device__ __forceinline__ int64_t coarse_row(int n, int set) { return ((int64_t)n * 2 + set) * (kCoarseMax + 1); }
+
+// Per-call state of cloud n, reset by the first kernel of every build (a whole workgroup of kSetupBlock threads).
+// One SET's partition state: ticket, crowded count, bin count, and the counters and cursors of the partition passes.
+__device__ __forceinline__ void reset_set_state(const GridWs& ws, int n, int set) {
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    ws.coarse_ticket[n * 2 + set] = 0;
+    ws.crowded_count[n * 2 + set] = 0;
+    ws.nbins[n * 2 + set] = 0;
+  }
+  for (int t = tid; t < kCoarseMax + 1; t += kSetupBlock) {
+    ws.coarse_count[coarse_row(n, set) + t] = 0;
+    ws.coarse_cursor[coarse_row(n, set) + t] = 0;
+  }
+}
+// The QUERY side: the searches' lists and set 1.  All a requery resets; grid_setup_kernel adds the point side.
+__device__ __forceinline__ void reset_query_state(const GridWs& ws, int n) {
+  if (threadIdx.x == 0) {
+    ws.fb_count[n] = 0;
+    ws.fb2_count[n] = 0;
+    ws.fb3_count[n] = 0;
+    ws.box_count[n] = 0;
+  }
+  reset_set_state(ws, n, 1);
+}
 
 // smallest x in [lo, hi] with cell_of(x) >= c, +inf if none
 __device__ float edge_bisect(int c, float lo, float hi, float inv_h, int G) {
@@ -54,8 +80,7 @@ __global__ __launch_bounds__(kBboxBlock) void grid_bbox_kernel(const float* __re
                                                              const int64_t* __restrict__ lengths2, int P2, int D,
                                                              float* __restrict__ bbox_part) {
   const int n = blockIdx.y;
-  int len2 = (int)lengths2[n];
-  len2 = len2 < 0 ? 0 : (len2 > P2 ? P2 : len2);
+  const int len2 = clamp_len(lengths2[n], P2);
   const int j0 = blockIdx.x * kBboxTile;
   if (j0 >= len2) return;  // (grid_setup reads the slots of the first ceil(len2 / tile) workgroups only)
   float mn[3], mx[3];
@@ -81,11 +106,8 @@ __global__ __launch_bounds__(kBboxBlock) void grid_bbox_kernel(const float* __re
   }
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-      mn[d] = fminf(mn[d], __shfl_xor(mn[d], off, kWave));
-      mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off, kWave));
-    }
+    mn[d] = wave_min(mn[d]);
+    mx[d] = wave_max(mx[d]);
   }
   __shared__ float s_mn[kBboxBlock / kWave][3], s_mx[kBboxBlock / kWave][3];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -117,10 +139,7 @@ __global__ __launch_bounds__(kSetupBlock) void grid_setup_kernel(
     float ball_radius, int ball_K, float ball_factor, int same, int bbox_slots, GridWs ws) {
   const int n = blockIdx.x;
   const int tid = threadIdx.x;
-  int len2 = (int)lengths2[n];
-  len2 = len2 < 0 ? 0 : (len2 > P2 ? P2 : len2);
-  int len1 = (int)lengths1[n];
-  len1 = len1 < 0 ? 0 : (len1 > P1 ? P1 : len1);
+  const int len2 = clamp_len(lengths2[n], P2), len1 = clamp_len(lengths1[n], P1);
   __shared__ GridCloud s_g;
   __shared__ float s_hi[3];
   __shared__ float s_box[kSetupBlock / kWave][6];
@@ -135,13 +154,7 @@ __global__ __launch_bounds__(kSetupBlock) void grid_setup_kernel(
       for (int k = 0; k < 6; ++k) v[k] = k < 3 ? fminf(v[k], slot[k]) : fmaxf(v[k], slot[k]);
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-#pragma unroll
-      for (int off = kWave / 2; off > 0; off >>= 1) {
-        const float u = __shfl_xor(v[k], off, kWave);
-        v[k] = k < 3 ? fminf(v[k], u) : fmaxf(v[k], u);
-      }
-    }
+    for (int k = 0; k < 6; ++k) v[k] = k < 3 ? wave_min(v[k]) : wave_max(v[k]);
     if ((tid & (kWave - 1)) == 0) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) s_box[tid / kWave][k] = v[k];
@@ -265,22 +278,11 @@ __global__ __launch_bounds__(kSetupBlock) void grid_setup_kernel(
     const float qnan = __uint_as_float(0x7fc00000u);
     ws.sorted[(int64_t)n * (P2 + kSortedPad) + P2] = make_float4(qnan, qnan, qnan, 0.0f);
     ws.grid_flag[n] = g.use_grid;
-    ws.fb_count[n] = 0;
-    ws.fb2_count[n] = 0;
-    ws.fb3_count[n] = 0;
     ws.rcount[n] = 0;
     ws.pool_top[n] = 0;
-    ws.box_count[n] = 0;
   }
-  for (int t = tid; t < 2 * (kCoarseMax + 1); t += kSetupBlock) {  // counters and cursors of the partition passes
-    ws.coarse_count[coarse_row(n, 0) + t] = 0;
-    ws.coarse_cursor[coarse_row(n, 0) + t] = 0;
-  }
-  if (tid < 2) {
-    ws.coarse_ticket[n * 2 + tid] = 0;
-    ws.crowded_count[n * 2 + tid] = 0;
-    ws.nbins[n * 2 + tid] = 0;
-  }
+  reset_set_state(ws, n, 0);
+  reset_query_state(ws, n);
   __syncthreads();
   if (s_g.use_grid) {
     float* __restrict__ ed = ws.edges + (int64_t)n * 3 * kEdgeStride;
@@ -306,12 +308,7 @@ __device__ void grid_chunk_prefix(const GridWs& ws, int N) {
       const GridCloud g = ws.cloud[n];
       if (g.use_grid) items = (g.len1 + kGridWave - 1) / kGridWave;
     }
-    int inc = items;  // inclusive wave scan
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int v = __shfl_up(inc, off, kWave);
-      if (lane >= off) inc += v;
-    }
+    const int inc = wave_inclusive_sum(items);
     if (n < N) ws.chunk_prefix[n + 1] = acc + inc;
     acc += __shfl(inc, kWave - 1, kWave);
   }
@@ -346,6 +343,30 @@ constexpr int kCrowded = 8192;       // records from which a bin is CROWDED: sor
 constexpr int kCrowdedSlice = 4096;  // records per slice
 constexpr int kFineMax = 1 << kFineLogMax;  // cells per bin cap: the LDS counters of one sort workgroup
 static_assert(kCoarseMax == kPartBlock, "the count launch's last tile scans one micro-bin per thread");
+
+// Row i of the query index space [0, P) when it gets no search: zeros for a padded query (knn_cpu.cpp:25-26; ball
+// query: -1), the whole-cloud list for a query of a cloud without a usable grid (ball query: left to the scan kernel).
+__device__ __forceinline__ void unsearched_row(const GridWs& ws, const GridCloud& g, int n, int i, int P, int K,
+                                               int64_t* __restrict__ idxs, float* __restrict__ dists) {
+  if (i < P && i >= g.len1) {
+    int64_t* __restrict__ zi = idxs + ((int64_t)n * P + i) * K;
+    float* __restrict__ zd = dists + ((int64_t)n * P + i) * K;
+    const int64_t pad = ws.ball ? -1 : 0;
+    for (int k = 0; k < K; ++k) {
+      zi[k] = pad;
+      zd[k] = 0.0f;
+    }
+  } else if (i < g.len1 && !g.use_grid && !ws.ball) {
+    const int pos = atomicAdd(ws.fb2_count + n, 1);
+    ws.fb2_list[(int64_t)n * P + pos] = i;
+  }
+}
+
+// cells [f0, f0 + nf) of bin b: its micro-bins' cells, cut at the cloud's last cell
+__device__ __forceinline__ void bin_cells(const GridCloud& g, const int* bfirst, int b, int& f0, int& nf) {
+  f0 = bfirst[b] << g.mshift;
+  nf = min((bfirst[b + 1] - bfirst[b]) << g.mshift, g.ncell - f0);
+}
 
 // atomicAdd(&counter[slot], 1) of every live lane of a wave; when all of them name the SAME counter (a bin whose
 // records sit in one cell: 64 LDS atomics on one address serialise) they spend one atomic.  Returns what the lane's
@@ -399,24 +420,8 @@ __global__ __launch_bounds__(kPartBlock) void grid_partition_kernel(const float*
   if (blockIdx.x * kPartTile >= P) return;
 
   if (PAD_ROWS && !SCATTER) {
-    // rows that get no search: zeros for padded queries (knn_cpu.cpp:25-26); whole-cloud list
-    // when this cloud has no usable grid
 #pragma unroll 4
-    for (int r = 0; r < kPartPerThread; ++r) {
-      const int i = i0 + r * kPartBlock;
-      if (i < P && i >= g.len1) {
-        int64_t* __restrict__ zi = idxs + ((int64_t)n * P + i) * K;
-        float* __restrict__ zd = dists + ((int64_t)n * P + i) * K;
-        const int64_t pad = ws.ball ? -1 : 0;
-        for (int k = 0; k < K; ++k) {
-          zi[k] = pad;
-          zd[k] = 0.0f;
-        }
-      } else if (i < g.len1 && !g.use_grid && !ws.ball) {
-        const int pos = atomicAdd(ws.fb2_count + n, 1);
-        ws.fb2_list[(int64_t)n * P + pos] = i;
-      }
-    }
+    for (int r = 0; r < kPartPerThread; ++r) unsearched_row(ws, g, n, i0 + r * kPartBlock, P, K, idxs, dists);
   }
   if (!g.use_grid || blockIdx.x * kPartTile >= len) return;
 
@@ -438,9 +443,7 @@ __global__ __launch_bounds__(kPartBlock) void grid_partition_kernel(const float*
     if (i < len) {
       float x, y, z;
       load_point3<D>(pts + ((int64_t)n * P + i) * D, x, y, z);
-      int cx, cy, cz;
-      point_cells(g, x, y, z, cx, cy, cz);
-      bin[r] = (cz * g.G[1] + cy) * g.G[0] + cx;
+      bin[r] = cell_id(g, x, y, z);
       key[r] = bin[r] >> mshift;
       if (SCATTER) {
         key[r] = s_group[key[r]];
@@ -482,24 +485,9 @@ __global__ __launch_bounds__(kPartBlock) void grid_partition_kernel(const float*
     if (s_last) {  // (workgroup-uniform)
       // BINS: consecutive micro-bins whose first record falls into the same block of kCoarsePoints records of the
       // cloud's cell order and that lie in the same block of kFineMax cells.
-      const int lane = tid & (kWave - 1), wave = tid / kWave;
       auto scan1 = [&](int v, int& total) {  // exclusive prefix of v over the workgroup (one value per thread)
-        int inc = v;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-          const int u = __shfl_up(inc, off, kWave);
-          if (lane >= off) inc += u;
-        }
         __syncthreads();  // (s_wsum free again)
-        if (lane == kWave - 1) s_wsum[wave] = inc;
-        __syncthreads();
-        int excl = inc - v;
-        total = 0;
-        for (int w = 0; w < kPartBlock / kWave; ++w) {
-          if (w < wave) excl += s_wsum[w];
-          total += s_wsum[w];
-        }
-        return excl;
+        return block_exclusive_sum<kPartBlock / kWave>(v, s_wsum, total);
       };
       const int m = tid;
       const int v = m < nmicro ? __hip_atomic_load(gcount + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
@@ -541,9 +529,8 @@ __global__ __launch_bounds__(kPartBlock) void grid_partition_kernel(const float*
       const int nc = min(s_ncrowd, kCrowdedMax);
       if (tid == 0) ws.crowded_count[n * 2 + set] = nc;
       for (int k = 0; k < nc; ++k) {  // (clist and gfirst: this workgroup's own writes, behind the barrier)
-        const int b = clist[k];
-        const int f0 = gfirst[b] << mshift;
-        const int nf = min((gfirst[b + 1] - gfirst[b]) << mshift, g.ncell - f0);
+        int f0, nf;
+        bin_cells(g, gfirst, clist[k], f0, nf);
         for (int f = tid; f < nf; f += kPartBlock) fine[f0 + f] = 0;
       }
     }
@@ -638,11 +625,11 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
   __shared__ int s_wsum[kSortBlock / kWave];
   __shared__ int s_list[kCrowdedMax];
   const int n = blockIdx.y, set = blockIdx.z + zbase;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = threadIdx.x;
   const GridCloud g = ws.cloud[n];
   const int len = set ? g.len1 : g.len2;
   if (!g.use_grid || len <= 0) return;
-  const int mshift = g.mshift, nbin = ws.nbins[n * 2 + set];
+  const int nbin = ws.nbins[n * 2 + set];
   const int* __restrict__ bfirst = ws.bin_first + coarse_row(n, set);
   const int* __restrict__ cstart = ws.coarse_start + coarse_row(n, set);
   int* __restrict__ cell_start = ws.cell_start + (int64_t)n * (ws.cell_cap + 1);
@@ -662,16 +649,8 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
     const int a0 = min(tid * per, nf), a1 = min(a0 + per, nf);
     int sum = 0;
     for (int f = a0; f < a1; ++f) sum += s_cnt[fine_slot(f)];
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int u = __shfl_up(inc, off, kWave);
-      if (lane >= off) inc += u;
-    }
-    if (lane == kWave - 1) s_wsum[wave] = inc;
-    __syncthreads();
-    int run = inc - sum;
-    for (int w = 0; w < wave; ++w) run += s_wsum[w];
+    int total;
+    int run = block_exclusive_sum<kSortBlock / kWave>(sum, s_wsum, total);
     for (int f = a0; f < a1; ++f) {
       const int c = s_cnt[fine_slot(f)];
       s_cnt[fine_slot(f)] = run;
@@ -717,15 +696,11 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
       for (int k = 0; k < ncrowd; ++k) listed = listed || s_list[k] == b;
       if (listed) continue;
     }
-    const int f0 = bfirst[b] << mshift;
-    const int nf = min((bfirst[b + 1] - bfirst[b]) << mshift, g.ncell - f0);
+    int f0, nf;
+    bin_cells(g, bfirst, b, f0, nf);
     for (int f = tid; f < nf; f += kSortBlock) s_cnt[fine_slot(f)] = 0;
     __syncthreads();
-    auto fine_of = [&](const float4 p) {  // the same expression as the partition pass
-      int cx, cy, cz;
-      point_cells(g, p.x, p.y, p.z, cx, cy, cz);
-      return (cz * g.G[1] + cy) * g.G[0] + cx - f0;
-    };
+    auto fine_of = [&](const float4 p) { return cell_id(g, p.x, p.y, p.z) - f0; };  // cell inside the bin
     // 1. histogram of the bin's cells.  A bin of up to 2048 records (the usual case) stays in registers with
     //    the rank the LDS atomic handed out; a longer one is read twice.
     const bool keep = cnt <= kKeep * kSortBlock;  // (workgroup-uniform)
@@ -745,20 +720,10 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
       for (int u = 0; u < kKeep; ++u)
         if (kf[u] >= 0) krank[u] = atomicAdd(&s_cnt[fine_slot(kf[u])], 1);
     } else {
-      // (workgroup-uniform trip count: wave_add shuffles)
-      for (int i0 = 0; i0 < cnt; i0 += 4 * kSortBlock) {
-        const int j = i0 + tid;
-        const bool l0 = j < cnt, l1 = j + kSortBlock < cnt, l2 = j + 2 * kSortBlock < cnt, l3 = j + 3 * kSortBlock < cnt;
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const float4 p0 = l0 ? tmp[start + j] : z;
-        const float4 p1 = l1 ? tmp[start + j + kSortBlock] : z;
-        const float4 p2 = l2 ? tmp[start + j + 2 * kSortBlock] : z;
-        const float4 p3 = l3 ? tmp[start + j + 3 * kSortBlock] : z;
-        wave_add(s_cnt, fine_slot(l0 ? fine_of(p0) : 0), l0);
-        wave_add(s_cnt, fine_slot(l1 ? fine_of(p1) : 0), l1);
-        wave_add(s_cnt, fine_slot(l2 ? fine_of(p2) : 0), l2);
-        wave_add(s_cnt, fine_slot(l3 ? fine_of(p3) : 0), l3);
-      }
+      // (for_each4 makes the same trips in every thread of the workgroup: wave_add shuffles)
+      for_each4<kSortBlock>(tmp + start, cnt, [&](const float4 p, int, bool live) {
+        wave_add(s_cnt, fine_slot(live ? fine_of(p) : 0), live);
+      });
     }
     __syncthreads();
     // 2. exclusive scan -> cell_start, refined-cell marks, cursors
@@ -770,23 +735,10 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
       for (int u = 0; u < kKeep; ++u)
         if (kf[u] >= 0) out[start + s_cnt[fine_slot(kf[u])] + krank[u]] = kp[u];
     } else {
-      for (int i0 = 0; i0 < cnt; i0 += 4 * kSortBlock) {  // (second read of the bin: L2)
-        const int j = i0 + tid;
-        const bool l0 = j < cnt, l1 = j + kSortBlock < cnt, l2 = j + 2 * kSortBlock < cnt, l3 = j + 3 * kSortBlock < cnt;
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const float4 p0 = l0 ? tmp[start + j] : z;
-        const float4 p1 = l1 ? tmp[start + j + kSortBlock] : z;
-        const float4 p2 = l2 ? tmp[start + j + 2 * kSortBlock] : z;
-        const float4 p3 = l3 ? tmp[start + j + 3 * kSortBlock] : z;
-        const int q0 = wave_add(s_cnt, fine_slot(l0 ? fine_of(p0) : 0), l0);
-        const int q1 = wave_add(s_cnt, fine_slot(l1 ? fine_of(p1) : 0), l1);
-        const int q2 = wave_add(s_cnt, fine_slot(l2 ? fine_of(p2) : 0), l2);
-        const int q3 = wave_add(s_cnt, fine_slot(l3 ? fine_of(p3) : 0), l3);
-        if (l0) out[start + q0] = p0;
-        if (l1) out[start + q1] = p1;
-        if (l2) out[start + q2] = p2;
-        if (l3) out[start + q3] = p3;
-      }
+      for_each4<kSortBlock>(tmp + start, cnt, [&](const float4 p, int, bool live) {  // (second read of the bin: L2)
+        const int q = wave_add(s_cnt, fine_slot(live ? fine_of(p) : 0), live);
+        if (live) out[start + q] = p;
+      });
     }
     __syncthreads();
   }
@@ -797,8 +749,8 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
   for (int k = 0; k < ncrowd; ++k) {
     const int b = s_list[k];
     const int start = cstart[b], cnt = cstart[b + 1] - start;
-    const int f0 = bfirst[b] << mshift;
-    const int nf = min((bfirst[b + 1] - bfirst[b]) << mshift, g.ncell - f0);
+    int f0, nf;
+    bin_cells(g, bfirst, b, f0, nf);
     const int slices = (cnt + kCrowdedSlice - 1) / kCrowdedSlice;
     for (int sl = blockIdx.x; sl < slices; sl += gridDim.x) {
       for (int f = tid; f < nf; f += kSortBlock) s_cnt[fine_slot(f)] = fine[f0 + f];
@@ -807,10 +759,7 @@ __global__ __launch_bounds__(kSortBlock) void grid_sort_kernel(GridWs ws, int P1
       const int j1 = min(cnt, (sl + 1) * kCrowdedSlice);
       for (int j = sl * kCrowdedSlice + tid; j < j1; j += kSortBlock) {
         const float4 p = tmp[start + j];
-        int cx, cy, cz;
-        point_cells(g, p.x, p.y, p.z, cx, cy, cz);
-        const int f = (cz * g.G[1] + cy) * g.G[0] + cx - f0;
-        out[start + s_cnt[fine_slot(f)] + rank[start + j]] = p;
+        out[start + s_cnt[fine_slot(cell_id(g, p.x, p.y, p.z) - f0)] + rank[start + j]] = p;
       }
       __syncthreads();
     }
@@ -916,22 +865,10 @@ __global__ __launch_bounds__(kSetupBlock) void grid_requery_kernel(const int64_t
                                                                 GridWs ws) {
   const int n = blockIdx.x, tid = threadIdx.x;
   if (tid == 0) {
-    int len1 = (int)lengths1[n];
-    len1 = len1 < 0 ? 0 : (len1 > P1 ? P1 : len1);
-    ws.cloud[n].len1 = len1;
+    ws.cloud[n].len1 = clamp_len(lengths1[n], P1);
     ws.cloud[n].same = same;
-    ws.fb_count[n] = 0;
-    ws.fb2_count[n] = 0;
-    ws.fb3_count[n] = 0;
-    ws.box_count[n] = 0;
-    ws.coarse_ticket[n * 2 + 1] = 0;
-    ws.crowded_count[n * 2 + 1] = 0;
-    ws.nbins[n * 2 + 1] = 0;
   }
-  for (int t = tid; t < kCoarseMax + 1; t += kSetupBlock) {  // counters and cursors of the query set's partition passes
-    ws.coarse_count[coarse_row(n, 1) + t] = 0;
-    ws.coarse_cursor[coarse_row(n, 1) + t] = 0;
-  }
+  reset_query_state(ws, n);
 }
 
 // what the count launch does besides counting, for calls that skip it: the chunk prefix, the rows that get no search
@@ -943,21 +880,8 @@ __global__ __launch_bounds__(kPartBlock) void grid_pad_prefix_kernel(GridWs ws, 
   const GridCloud g = ws.cloud[n];
   if (g.len1 >= P1 && g.use_grid) return;  // (the usual case: nothing to pad, nothing to list)
   constexpr int kTile = kPartBlock * kCountPerThread;
-  for (int r = 0; r < kCountPerThread; ++r) {
-    const int i = blockIdx.x * kTile + r * kPartBlock + tid;
-    if (i < P1 && i >= g.len1) {
-      int64_t* __restrict__ zi = idxs + ((int64_t)n * P1 + i) * K;
-      float* __restrict__ zd = dists + ((int64_t)n * P1 + i) * K;
-      const int64_t pad = ws.ball ? -1 : 0;
-      for (int k = 0; k < K; ++k) {
-        zi[k] = pad;
-        zd[k] = 0.0f;
-      }
-    } else if (i < g.len1 && !g.use_grid && !ws.ball) {
-      const int pos = atomicAdd(ws.fb2_count + n, 1);
-      ws.fb2_list[(int64_t)n * P1 + pos] = i;
-    }
-  }
+  for (int r = 0; r < kCountPerThread; ++r)
+    unsearched_row(ws, g, n, blockIdx.x * kTile + r * kPartBlock + tid, P1, K, idxs, dists);
 }
 
 // level 1: a new query set against the built point side; level 2: the same query set again

@@ -14,31 +14,13 @@
 //                  LDS, exclusive scan -> sub_start table, scatter into a scratch copy, copy back.
 // Clouds without over-full cells cost one empty launch.
 #include "grid.h"
+#include "wave.h"
 
 namespace pointops {
 
 constexpr int kRefineBlock = 1024;
 constexpr int kRefineWgs = 8;  // workgroups per cloud walking the cloud's list of refined cells (each claims 128 KB
                                // of LDS: 256 of them are one round of the chip, and an empty list costs one round)
-
-// fn(record, i) for the `count` records behind `src`, the workgroup's threads striding over them with FOUR loads in
-// flight each (a cell of 75 000 points is 73 strides of one workgroup: one load at a time made every pass ~50 us)
-template <typename Fn>
-__device__ __forceinline__ void for_each4(const float4* __restrict__ src, int count, Fn fn) {
-  for (int i0 = threadIdx.x; i0 < count; i0 += 4 * kRefineBlock) {
-    float4 p[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = i0 + u * kRefineBlock;
-      if (j < count) p[u] = src[j];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = i0 + u * kRefineBlock;
-      if (j < count) fn(p[u], j);
-    }
-  }
-}
 
 template <int D>
 __global__ __launch_bounds__(kRefineBlock) void grid_refine_build_kernel(GridWs ws, int P2) {
@@ -59,7 +41,8 @@ __global__ __launch_bounds__(kRefineBlock) void grid_refine_build_kernel(GridWs 
     const int nsub = s * s * s;
     // 1. mean and sigma of the cell's points (fp64 sums: exactness is not needed, robustness is)
     double acc[6] = {0, 0, 0, 0, 0, 0};
-    for_each4(rec + start, count, [&](const float4 p, int) {
+    for_each4<kRefineBlock>(rec + start, count, [&](const float4 p, int, bool live) {
+      if (!live) return;
       const double v[3] = {p.x, p.y, p.z};
 #pragma unroll
       for (int d = 0; d < D; ++d) {
@@ -68,10 +51,7 @@ __global__ __launch_bounds__(kRefineBlock) void grid_refine_build_kernel(GridWs 
       }
     });
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-#pragma unroll
-      for (int off = kWave / 2; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, kWave);
-    }
+    for (int k = 0; k < 6; ++k) acc[k] = wave_sum(acc[k]);
     __syncthreads();  // (previous cell's users of the shared arrays are done)
     if (lane == 0) {
 #pragma unroll
@@ -114,7 +94,9 @@ __global__ __launch_bounds__(kRefineBlock) void grid_refine_build_kernel(GridWs 
       return (iz * s + iy) * s + ix;
     };
     // 2. histogram
-    for_each4(rec + start, count, [&](const float4 p, int) { atomicAdd(&s_hist[sub_index(p)], 1); });
+    for_each4<kRefineBlock>(rec + start, count, [&](const float4 p, int, bool live) {
+      if (live) atomicAdd(&s_hist[sub_index(p)], 1);
+    });
     __syncthreads();
     // 3. exclusive scan of nsub counters (each thread a contiguous slice) -> table in the pool, cursors in LDS
     int* __restrict__ table = ws.pool + (int64_t)n * ws.pool_cap + dp->pool_off;
@@ -122,16 +104,8 @@ __global__ __launch_bounds__(kRefineBlock) void grid_refine_build_kernel(GridWs 
     const int b0 = tid * per, b1 = min(b0 + per, nsub);
     int sum = 0;
     for (int b = b0; b < b1; ++b) sum += s_hist[b];
-    int inc = sum;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int v = __shfl_up(inc, off, kWave);
-      if (lane >= off) inc += v;
-    }
-    if (lane == kWave - 1) s_wsum[wave] = inc;
-    __syncthreads();
-    int run = inc - sum;
-    for (int w = 0; w < wave; ++w) run += s_wsum[w];
+    int total;
+    int run = block_exclusive_sum<kRefineBlock / kWave>(sum, s_wsum, total);
     for (int b = b0; b < b1; ++b) {
       const int cnt = s_hist[b];
       table[b] = run;
@@ -141,10 +115,14 @@ __global__ __launch_bounds__(kRefineBlock) void grid_refine_build_kernel(GridWs 
     if (tid == kRefineBlock - 1) table[nsub] = count;
     __syncthreads();
     // 4. scatter into the scratch copy, then back into the cell's range
-    for_each4(rec + start, count, [&](const float4 p, int) { tmp[start + atomicAdd(&s_hist[sub_index(p)], 1)] = p; });
+    for_each4<kRefineBlock>(rec + start, count, [&](const float4 p, int, bool live) {
+      if (live) tmp[start + atomicAdd(&s_hist[sub_index(p)], 1)] = p;
+    });
     __threadfence_block();
     __syncthreads();
-    for_each4(tmp + start, count, [&](const float4 p, int i) { rec[start + i] = p; });
+    for_each4<kRefineBlock>(tmp + start, count, [&](const float4 p, int i, bool live) {
+      if (live) rec[start + i] = p;
+    });
   }
 }
 

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kGridWave) void knn_grid_box_kernel(
     // radius from the local density: points expected inside the ball ~ 2.5 K
     float r;
     {
-      const int cell = (cc[2] * g.G[1] + cc[1]) * g.G[0] + cc[0];
+      const int cell = cell_index(g, cc[0], cc[1], cc[2]);
       const int ref = active ? rref[cell] : -1;
       float vol = 1.0f, cntf;
       if (ref >= 0) {

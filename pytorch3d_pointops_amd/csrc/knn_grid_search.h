@@ -6,6 +6,7 @@
 #include "grid.h"
 #include "knn_common.h"
 #include "sort_net.h"
+#include "wave.h"
 
 #include <type_traits>
 
@@ -617,12 +618,7 @@ __global__ __launch_bounds__(kWaveKernelBlock) void knn_grid_wave_kernel(
             src = cstart[rowbase + X0];
             len_r = cstart[rowbase + X1 + 1] - src;
           }
-          int inc = len_r;  // inclusive wave scan
-#pragma unroll
-          for (int off = 1; off < kWave; off <<= 1) {
-            const int v = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += v;
-          }
+          const int inc = wave_inclusive_sum(len_r);
           if (rr < nblk) {
             rs[rr] = src;
             ro[rr + 1] = T + inc;

@@ -15,6 +15,7 @@
 #include "grid.h"
 #include "knn_common.h"
 #include "sort_net.h"
+#include "wave.h"
 
 namespace pointops {
 
@@ -151,12 +152,7 @@ __global__ __launch_bounds__(kWsBlock, 2) void knn_grid_wsort_kernel(
         src = cstart[rowbase + X0];
         len = cstart[rowbase + X1 + 1] - src;
       }
-      int inc = len;
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) {
-        const int v = __shfl_up(inc, o, kGridWave);
-        if (lane >= o) inc += v;
-      }
+      const int inc = wave_inclusive_sum<32>(len);  // (nrows <= 25 lanes hold a row)
       const int T = __shfl(inc, kWsMaxRows - 1, kGridWave);  // (lanes >= nrows carry the total on)
       if (T > kWsMaxStream) break;  // (a cluster: the all-pairs list is cheaper than dozens of sorts)
       // The stream is consumed in CHUNKS: the first fills all 2048 key slots; every further one (cubes with more

@@ -1418,6 +1418,34 @@ def test_knn_grid_many_crowded_bins(dev, D):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("norm", [2, 1])
+def test_knn_grid_long_bin(dev, oracle, norm):
+    """The LONG-bin path of the sort pass (grid_sort_kernel: a bin of more than 2048 records that is not crowded is
+    read twice, its cells counted and its records placed through wave_add, whose lanes mostly name the same cell).
+    Half of each set sits in a cube of edge 1e-5 -- one cell, or very few, of a grid whose cells are ~0.1 wide -- so
+    that cell's bin holds at least the 3000 clustered records and at most the set's 6000 < 8192: above the register
+    path's 2048, below the crowded bins' slices (points of both clouds, queries of cloud 0; cloud 1 has 100 queries and
+    5000 points).  The diagnostics confirm that no bin was listed as crowded; indices and distance bits equal the
+    oracle, ragged lengths included."""
+    from pytorch3d_pointops_amd import _C
+    from pytorch3d_pointops_amd.functions import knn_points
+
+    N, P, K = 2, 6000, 4
+    a, b = cases.cloud(2801, (N, P, 3)), cases.cloud(2802, (N, P, 3))
+    for pts, seed in ((a, 2803), (b, 2804)):
+        centre = cases.cloud(seed, (N, 1, 3)) * np.float32(0.5) + np.float32(0.25)
+        pts[:, :3000] = pts[:, :3000] * np.float32(1e-5) + centre
+    l1, l2 = np.array([P, 100]), np.array([P, 5000])
+    args = (G(a, dev), G(b, dev), G(l1, dev), G(l2, dev))
+    r = knn_points(*args, norm=norm, K=K, version=3)
+    st = _C.knn_grid_stats(*args, norm, K)[2].cpu().numpy()
+    assert (st[:, 4] == 1).all() and (st[:, 12] == 0).all() and (st[:, 13] == 0).all(), st
+    oi, od = oracle.knn_points_idx(a, b, l1, l2, norm, K)
+    assert np.array_equal(r.idx.cpu().numpy(), oi)
+    assert np.array_equal(bits(r.dists.cpu().numpy()), bits(od))
+
+
+@pytest.mark.gpu
 def test_chamfer_backward_accumulate_equals_sum_of_directions(dev):
     """pointops_chamfer_backward_accumulate (include/pointops_amd.h): the reverse direction's gradients ADDED into the
     buffers the forward direction's call filled equal the sum of two separate backward calls (the reference sums the
