@@ -406,6 +406,63 @@ int pointops_spfh(const float* points, const float* normals, const int64_t* idx,
 int pointops_fpfh(const float* points, const int64_t* idx, const int64_t* lengths, const float* spfh, int64_t N,
                   int64_t P, int64_t K, float* fpfh, void* stream);
 
+/*
+ * RANSAC over putative correspondences: the robust estimator between the descriptor matches (mutual nearest
+ * neighbours of FPFH rows: mostly wrong on real scans) and pointops_points_alignment / pointops_icp_iteration -- device
+ * half of functions/ransac.py.  The semantics are this library's own; all fp32 arithmetic is unfused and in the order
+ * written.  float32, three dimensions, proper rotations only (three pairs cannot tell a rotation from a reflection).
+ *   X (N,P1,3), Y (N,P2,3) fp32; corr (N,P1) int64 or NULL: row i of X is matched to row corr[n,i] of Y (NULL: to row i,
+ *   then P2 == P1); lengths1, lengths2 (N,) or NULL (= P1, P2; clamped into [0,P]); samples_in (N,H,3) int64 or NULL.
+ *   1. Valid correspondences: row i of cloud n is VALID when i < lengths1[n] and 0 <= corr[n,i] < lengths2[n].  The
+ *      valid rows in ascending order are v[0..M_n); two rows may share a target.
+ *   2. Draws (samples_in == NULL and M_n >= 3): with mix(x) = { x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ *      x *= 0x846ca68b; x ^= x >> 16 } on uint32 (lowbias32) and g = first_cloud + n,
+ *        hash32(seed, g, h, j) = mix(mix(mix(mix(mix((uint32)seed + 0x9e3779b9) ^ (uint32)(seed >> 32)) ^ g) ^ h) ^ j),
+ *      u_j = hash32(seed, g, h, j) for j = 0, 1, 2 and mulhi(a,b) = ((uint64)a * b) >> 32:
+ *        i0 = mulhi(u0, M);  i1 = mulhi(u1, M-1), i1 += (i1 >= i0);
+ *        i2 = mulhi(u2, M-2), i2 += (i2 >= min(i0,i1)), then i2 += (i2 >= max(i0,i1)).
+ *      The triple of hypothesis h is the rows v[i0], v[i1], v[i2]: distinct, uniform.  first_cloud is the index of
+ *      cloud 0 of this call in the caller's batch, so a batch cut into several calls draws what one call would.
+ *      With samples_in the triple is samples_in[n,h,:] and nothing is drawn.
+ *   3. A hypothesis is VALID when its three rows are distinct valid correspondences (only samples_in can violate that;
+ *      a cloud with M_n < 3 and no samples_in has none) and, when estimate_scale == 0 and edge_length_ratio > 0, every
+ *      pair (a,b) of (0,1), (0,2), (1,2) passes the edge test: with q = ratio * ratio (fp32), dx = x_a - x_b,
+ *      lx = (dx0*dx0 + dx1*dx1) + dx2*dx2 and ly likewise from the matched rows of Y:  lx >= q*ly and ly >= q*lx.
+ *   4. The transform of a valid hypothesis is pointops_points_alignment of its three pairs with unit weights, eps 1e-9
+ *      and no reflection: the moments about pair 0 in fp64, the fp64 solve, one rounding to fp32.  An invalid one has
+ *      R = I, T = 0, s = 1 and the count -1.
+ *   5. Score: A[j][k] = s * R[j][k] (fp32); for every valid row  r_k = ((x0*A[0][k] + x1*A[1][k]) + x2*A[2][k]) + T[k],
+ *      e = r - y, d2 = (e0*e0 + e1*e1) + e2*e2; the row is an inlier iff d2 <= thr2 = inlier_threshold *
+ *      inlier_threshold (formed once in fp32).  count = the number of inliers (int32).
+ *   6. best[n] = the valid hypothesis with the largest count, the lowest index among equals; -1 when none is valid.
+ *   7. Evaluation of a transform: the same formulas give the mask over all P1 rows (0 for rows that are not valid), the
+ *      count and rmse = sqrt(sum over the inliers of d2 / max(count, 1)), the sum in fp64 in a fixed order.
+ *   8. The winner is evaluated; then, refine_steps times, per cloud and on the device: fit pointops_points_alignment
+ *      with idx = corr, weights = the current mask as 0/1, lengths1 and eps 1e-9; evaluate the fit; accept it (transform,
+ *      mask, count, rmse) iff its count >= the current count, else keep what is there and ignore the later steps.
+ *   9. best[n] == -1 gives R = I, T = 0, s = 1, an all-zero mask, num_inliers 0 and rmse 0.
+ *   Outputs: R (N,3,3), T (N,3), s (N,) fp32, inlier_mask (N,P1) one byte 0/1 per row, num_inliers (N,) int64, rmse (N,)
+ *   fp32, best (N,) int64; optional (NULL skips them) counts (N,H) int32, hyp_R (N,H,3,3), hyp_T (N,H,3), hyp_s (N,H)
+ *   fp32 and samples_out (N,H,3) int64: the rows of X of every triple (-1 where nothing was drawn).  Every output is
+ *   fully written.  No atomics, nothing synchronises, nothing is read back: results are bit-reproducible.
+ *   workspace: pointops_ransac_workspace_bytes(N, P1, H); a short or null one is POINTOPS_EWORKSPACE with nothing
+ *   written.  0 <= N < 65536 (as for pointops_points_alignment, which it calls; a bigger batch goes in slices with
+ *   first_cloud), P1 <= 65535 * pointops_ransac_chunk(), P2 < 2^30, 1 <= H <= 2^24, inlier_threshold >= 0,
+ *   0 <= edge_length_ratio <= 1, refine_steps >= 0, first_cloud >= 0: anything else is POINTOPS_EINVAL with nothing
+ *   launched.  N == 0 launches nothing; P1 == 0 gives the result of (9), whatever corr and P2 are (an empty table has
+ *   no address) and without a refit.
+ *   pointops_ransac_chunk(): the number of records one scoring workgroup walks (the sizes around which tests probe).
+ */
+int64_t pointops_ransac_chunk(void);
+size_t pointops_ransac_workspace_bytes(int64_t N, int64_t P1, int64_t H);
+int pointops_ransac_alignment(const float* X, const float* Y, const int64_t* corr, const int64_t* lengths1,
+                              const int64_t* lengths2, const int64_t* samples_in, int64_t N, int64_t P1, int64_t P2,
+                              int64_t H, int64_t seed, int64_t first_cloud, float inlier_threshold,
+                              float edge_length_ratio, int estimate_scale, int refine_steps, float* R, float* T,
+                              float* s, uint8_t* inlier_mask, int64_t* num_inliers, float* rmse, int64_t* best,
+                              int32_t* counts, float* hyp_R, float* hyp_T, float* hyp_s, int64_t* samples_out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

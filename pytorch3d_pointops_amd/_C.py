@@ -75,6 +75,11 @@ _SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "pointops_spfh": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "pointops_fpfh": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "pointops_ransac_chunk": (_i64, []),
+    "pointops_ransac_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "pointops_ransac_alignment": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32,
+                                         _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _sz, _vp]),
     "pointops_chamfer_workspace_bytes": (_sz, [_i64, _i64]),
     "pointops_chamfer_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int,
                                         _int, _vp, _vp, _sz, _vp]),

@@ -22,6 +22,7 @@
 //                      above 4096 points;  fps_ppt=4|8|16 forces it
 //   fps_mode=0|1|2     FPS clusters: round-robin members / XCD-local members / XCD-local + L2 exchange
 //   fps_spin_limit=N   FPS exchange spin bound (tests force the timeout repair path with 0)
+//   ransac_lds=1       RANSAC scoring: the records through an LDS tile instead of the scalar path (ransac.hip)
 #pragma once
 
 namespace pointops {
