@@ -463,6 +463,32 @@ int pointops_ransac_alignment(const float* X, const float* Y, const int64_t* cor
                               int32_t* counts, float* hyp_R, float* hyp_T, float* hyp_s, int64_t* samples_out,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * DBSCAN / Euclidean clustering: a raw scan cut into objects -- device half of functions/cluster.py.  The semantics
+ * are this library's own (they equal scikit-learn's DBSCAN and Open3D's cluster_dbscan except for pairs at exactly
+ * eps); all fp32 arithmetic is unfused and in the order written.  Integer outputs only: bit-reproducible.
+ *   points (N,P,D) fp32, D in 1..3; lengths (N,) or NULL (= P; clamped into [0,P]).  Per cloud n, over its first
+ *   lengths[n] points:
+ *   1. r2 = eps * eps (fp32).  d2(i,j) = (dx*dx + dy*dy) + dz*dz over the D coordinates, dx = x_i - x_j: ball query's
+ *      expression, symmetric bit for bit.  i and j are NEIGHBOURS iff d2(i,j) < r2 (ball query's comparison); a point
+ *      is its own neighbour unless a coordinate is not finite (or r2 underflows to 0).
+ *   2. i is a CORE point iff it has at least min_points neighbours, itself included.
+ *   3. CLUSTERS: the connected components of the neighbour graph restricted to the core points, numbered 0, 1, ... in
+ *      the order of their smallest member index.
+ *   4. BORDER: a non-core point with at least one core neighbour takes the smallest label among its core neighbours'
+ *      clusters.  NOISE: every other point, and every padding row, gets label -1.
+ *   min_points == 1 is Euclidean clustering: the connected components of the radius graph.
+ *   Outputs: labels (N,P) int64, num_clusters (N,) int64, core_mask (N,P) one byte 0/1 per row (0 on padding rows).
+ *   Every output is fully written.  Nothing synchronises, nothing is read back.
+ *   workspace: pointops_cluster_workspace_bytes(N, P); a short or null one is POINTOPS_EWORKSPACE with nothing written.
+ *   0 <= N < 65536 (a bigger batch goes in slices), 0 <= P < 2^30, 1 <= D <= 3, eps finite and > 0, min_points >= 1:
+ *   anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing; P == 0 writes num_clusters = 0.
+ */
+size_t pointops_cluster_workspace_bytes(int64_t N, int64_t P);
+int pointops_cluster_dbscan(const float* points, const int64_t* lengths, int64_t N, int64_t P, int64_t D, float eps,
+                            int64_t min_points, int64_t* labels, int64_t* num_clusters, uint8_t* core_mask,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

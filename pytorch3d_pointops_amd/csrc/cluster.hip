@@ -1,0 +1,331 @@
+// cluster.hip -- DBSCAN / Euclidean clustering of a batch of clouds (C ABI: pointops_cluster_dbscan; device half of
+// functions/cluster.py).  The definition is the comment block of the entry in include/pointops_amd.h: neighbours are
+// the pairs with ball query's `dist2 < eps * eps` (point_dist<D, 2> of grid.h, unfused fp32), a core point has at least
+// min_points of them (itself included), clusters are the connected components of the neighbour graph on the core
+// points numbered by their smallest member, a border point takes the smallest label among its core neighbours.
+//
+// A fixed sequence of launches, stream-ordered, nothing read back; the kernel boundary is the only synchronisation:
+//   lengths   the cloud lengths clamped into [0, P] (a null `lengths` = P), for grid_build and every pass
+//   grid      grid_build with same = true, h_min = 1.001 eps, refine = -1 (the KNN-style workspace): the cloud sorted
+//             by cells at least eps wide -- for clouds of kClusterGridMinPoints points and more
+//   count     one lane per point: neighbours counted up to min_points -> core_mask; parent[i] = i
+//   union     core lanes walk again: uf_union(i, j) for every core neighbour j < i (cluster_union.h: lock-free,
+//             relaxed agent-scope atomics only, the root of a component = its smallest index)
+//   flatten   core: label = find(i); non-core: the smallest root among the core neighbours, or -1.  Its own launch:
+//             the roots it reads are final only once every hook of the union launch has been made.
+//   scan      one workgroup per cloud: the roots (label == own index) ranked in index order -> rank[], num_clusters
+//   relabel   label = rank[root]
+// A WALK is ball_grid_lane_kernel's: the nine x-runs of the 3x3x3 cube around the lane's cell, taken only under that
+// kernel's certificate `whole || box_lower_bound<2>(...) >= r2` (every unvisited point has dist2 >= r2).  A lane without
+// the certificate, and every lane of a cloud whose grid was refused (non-finite coordinates, cell caps) or that is too
+// small for one, walks the raw cloud instead: all pairs, the same comparison, so which path a lane takes depends on
+// the input alone and never changes a result.  POINTOPS_DEBUG=cluster_grid=0 sends every cloud that way.
+#include <limits.h>
+
+#include "cluster_union.h"
+#include "debug.h"
+#include "grid.h"
+#include "wave.h"
+
+namespace pointops {
+
+constexpr int kClBlock = 256;
+constexpr int kClScanBlock = 1024;
+constexpr float kClusterCellTarget = 2.0f;    // density floor of the cell size (ball query's); eps usually decides
+constexpr int kClusterGridMinPoints = 512;    // smaller clouds: all pairs (the build's fixed passes cost more)
+
+struct ClusterView {
+  const float* points;       // (N, P, D)
+  const int64_t* len;        // (N,) clamped
+  const GridCloud* clouds;   // grid state: null when the call builds no grid
+  const float* edges;
+  const int* cell_start;
+  const float4* sorted;
+  int cell_cap, P;
+  float r2;
+};
+
+template <int D>
+struct ClusterLane {
+  int i;            // the point's index in its cloud
+  float x, y, z;
+  bool cube;        // walk the 3x3x3 cube (certified); else the raw cloud
+  int cy, cz, X0, X1;
+};
+
+// lane t of cloud n: position t of the cell order where the cloud has a grid, point t where it has none
+template <int D>
+__device__ __forceinline__ ClusterLane<D> cluster_lane(const ClusterView& v, const GridCloud& g, bool grid, int n,
+                                                       int t) {
+  ClusterLane<D> L;
+  L.cy = L.cz = L.X0 = L.X1 = 0;
+  if (grid) {
+    const float4 q = v.sorted[(int64_t)n * (v.P + kSortedPad) + t];
+    L.x = q.x, L.y = q.y, L.z = q.z;
+    L.i = __float_as_int(q.w);
+    int cx;
+    point_cells(g, L.x, L.y, L.z, cx, L.cy, L.cz);
+    L.X0 = max(cx - 1, 0), L.X1 = min(cx + 1, g.G[0] - 1);
+    const int Y0 = max(L.cy - 1, 0), Y1 = min(L.cy + 1, g.G[1] - 1);
+    const int Z0 = max(L.cz - 1, 0), Z1 = min(L.cz + 1, g.G[2] - 1);
+    bool whole;
+    const float lb = box_lower_bound<2>(g, v.edges + (int64_t)n * 3 * kEdgeStride, L.x, L.y, L.z, L.X0, L.X1, Y0, Y1,
+                                        Z0, Z1, whole);
+    L.cube = whole || lb >= v.r2;  // every unvisited point has computed dist2 >= lb
+  } else {
+    load_point3<D>(v.points + ((int64_t)n * v.P + t) * D, L.x, L.y, L.z);
+    L.i = t;
+    L.cube = false;
+  }
+  return L;
+}
+
+// fn(j) for every neighbour j of the lane (dist2 < r2, the lane itself included), until fn returns false
+template <int D, typename Fn>
+__device__ __forceinline__ void cluster_walk(const ClusterView& v, const GridCloud& g, const ClusterLane<D>& L, int n,
+                                             int len, Fn fn) {
+  if (L.cube) {
+    const float4* __restrict__ sp = v.sorted + (int64_t)n * (v.P + kSortedPad);
+    const int* __restrict__ cstart = v.cell_start + (int64_t)n * (v.cell_cap + 1);
+    for (int dz = -1; dz <= 1; ++dz) {
+      const int z = L.cz + dz;
+      if (z < 0 || z >= g.G[2]) continue;
+      for (int dy = -1; dy <= 1; ++dy) {
+        const int y = L.cy + dy;
+        if (y < 0 || y >= g.G[1]) continue;
+        const int rowbase = (z * g.G[1] + y) * g.G[0];
+        const int s = cstart[rowbase + L.X0], e = cstart[rowbase + L.X1 + 1];
+        for (int k = s; k < e; ++k) {
+          const float4 c = sp[k];
+          if (point_dist<D, 2>(L.x, L.y, L.z, c) < v.r2) {
+            if (!fn(__float_as_int(c.w))) return;
+          }
+        }
+      }
+    }
+  } else {
+    const float* __restrict__ pts = v.points + (int64_t)n * v.P * D;
+    for (int j = 0; j < len; ++j) {
+      float4 c;
+      load_point3<D>(pts + (int64_t)j * D, c.x, c.y, c.z);
+      if (point_dist<D, 2>(L.x, L.y, L.z, c) < v.r2) {
+        if (!fn(j)) return;
+      }
+    }
+  }
+}
+
+// (cloud, lane, length, grid state) of a thread of the per-point launches; false: nothing to walk
+struct ClusterItem {
+  int n, t, len;
+  bool grid;
+};
+__device__ __forceinline__ ClusterItem cluster_item(const ClusterView& v, GridCloud& g) {
+  ClusterItem it;
+  it.n = blockIdx.y;
+  it.t = blockIdx.x * kClBlock + threadIdx.x;
+  it.len = (int)v.len[it.n];
+  it.grid = false;
+  if (v.clouds != nullptr) {
+    g = v.clouds[it.n];
+    it.grid = g.use_grid != 0;
+  }
+  return it;
+}
+
+__global__ __launch_bounds__(kClBlock) void cluster_lengths_kernel(const int64_t* __restrict__ lengths, int N, int P,
+                                                                 int64_t* __restrict__ len) {
+  const int n = blockIdx.x * kClBlock + threadIdx.x;
+  if (n >= N) return;
+  const int64_t l = lengths != nullptr ? lengths[n] : (int64_t)P;
+  len[n] = l < 0 ? 0 : (l > P ? P : l);
+}
+
+template <int D>
+__global__ __launch_bounds__(kClBlock) void cluster_count_kernel(ClusterView v, int min_points,
+                                                               uint8_t* __restrict__ core_mask,
+                                                               int* __restrict__ parent) {
+  GridCloud g = {};
+  const ClusterItem it = cluster_item(v, g);
+  if (it.t >= v.P) return;
+  if (it.t >= it.len) {
+    core_mask[(int64_t)it.n * v.P + it.t] = 0;  // padding rows
+    return;
+  }
+  const ClusterLane<D> L = cluster_lane<D>(v, g, it.grid, it.n, it.t);
+  int cnt = 0;
+  cluster_walk<D>(v, g, L, it.n, it.len, [&](int) { return ++cnt < min_points; });
+  core_mask[(int64_t)it.n * v.P + L.i] = cnt >= min_points ? 1 : 0;
+  parent[(int64_t)it.n * v.P + L.i] = L.i;
+}
+
+template <int D>
+__global__ __launch_bounds__(kClBlock) void cluster_union_kernel(ClusterView v, const uint8_t* __restrict__ core_mask,
+                                                               int* parent) {
+  GridCloud g = {};
+  const ClusterItem it = cluster_item(v, g);
+  if (it.t >= it.len) return;
+  const ClusterLane<D> L = cluster_lane<D>(v, g, it.grid, it.n, it.t);
+  const uint8_t* __restrict__ core = core_mask + (int64_t)it.n * v.P;
+  if (!core[L.i]) return;
+  int* const par = parent + (int64_t)it.n * v.P;
+  int up = L.i;  // an ancestor-or-self of this point: the unions start from it, not from the point every time
+  cluster_walk<D>(v, g, L, it.n, it.len, [&](int j) {
+    if (j < L.i && core[j]) up = uf_union(par, up, j);  // (every edge once: from its larger end)
+    return true;
+  });
+}
+
+template <int D>
+__global__ __launch_bounds__(kClBlock) void cluster_flatten_kernel(ClusterView v, const uint8_t* __restrict__ core_mask,
+                                                                 int* parent, int64_t* __restrict__ labels) {
+  GridCloud g = {};
+  const ClusterItem it = cluster_item(v, g);
+  if (it.t >= v.P) return;
+  if (it.t >= it.len) {
+    labels[(int64_t)it.n * v.P + it.t] = -1;  // padding rows
+    return;
+  }
+  const ClusterLane<D> L = cluster_lane<D>(v, g, it.grid, it.n, it.t);
+  const uint8_t* __restrict__ core = core_mask + (int64_t)it.n * v.P;
+  int* const par = parent + (int64_t)it.n * v.P;
+  int root;
+  if (core[L.i]) {
+    root = uf_find(par, L.i);
+  } else {
+    root = INT_MAX;  // the smallest root = the smallest label: clusters are numbered by their smallest member
+    cluster_walk<D>(v, g, L, it.n, it.len, [&](int j) {
+      if (core[j]) root = min(root, uf_find(par, j));
+      return true;
+    });
+    if (root == INT_MAX) root = -1;
+  }
+  labels[(int64_t)it.n * v.P + L.i] = root;
+}
+
+// One workgroup per cloud loops over tiles of the index space: rank[r] = roots below r, for every root r.
+__global__ __launch_bounds__(kClScanBlock) void cluster_scan_kernel(const int64_t* __restrict__ len, int P,
+                                                                  const int64_t* __restrict__ labels,
+                                                                  int* __restrict__ rank,
+                                                                  int64_t* __restrict__ num_clusters) {
+  __shared__ int s_wsum[kClScanBlock / kWave];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int length = (int)len[n];
+  int base = 0;
+  for (int i0 = 0; i0 < length; i0 += kClScanBlock) {
+    const int i = i0 + tid;
+    const int flag = (i < length && labels[(int64_t)n * P + i] == (int64_t)i) ? 1 : 0;
+    int total;
+    const int excl = block_exclusive_sum<kClScanBlock / kWave>(flag, s_wsum, total);
+    if (flag) rank[(int64_t)n * P + i] = base + excl;
+    base += total;
+    __syncthreads();  // (s_wsum free again)
+  }
+  if (tid == 0) num_clusters[n] = base;
+}
+
+__global__ __launch_bounds__(kClBlock) void cluster_relabel_kernel(const int64_t* __restrict__ len, int P,
+                                                                 const int* __restrict__ rank, int64_t* labels) {
+  const int n = blockIdx.y, i = blockIdx.x * kClBlock + threadIdx.x;
+  if (i >= (int)len[n]) return;
+  const int64_t root = labels[(int64_t)n * P + i];
+  if (root >= 0) labels[(int64_t)n * P + i] = rank[(int64_t)n * P + root];
+}
+
+static bool cluster_shape_ok(int64_t N, int64_t P, int64_t D) {
+  // (a cloud is a grid's y coordinate; point indices are ints)
+  return N >= 0 && N < 65536 && P >= 0 && P < (1LL << 30) && D >= 1 && D <= 3;
+}
+
+// whether the call builds grids (the per-cloud decision is grid_build's, on the device)
+static bool cluster_uses_grid(int64_t N, int64_t P) {
+  const long force = debug_knob("cluster_grid", -1);  // 0 = never, 1 = whenever the shape allows (tests)
+  if (force == 0 || N <= 0 || P <= 0 || P > knn_grid_max_points()) return false;
+  return force == 1 || P >= kClusterGridMinPoints;
+}
+
+struct ClusterLayout {
+  int64_t* len;  // (N,)
+  int* parent;   // (N, P)
+  int* rank;     // (N, P)
+  char* grid;    // grid_carve's
+  size_t bytes;
+};
+
+static ClusterLayout cluster_layout(void* ws, int64_t N, int64_t P, bool grid) {
+  Carver c(ws);
+  ClusterLayout l;
+  l.len = (int64_t*)c.take(sizeof(int64_t) * (size_t)N);
+  l.parent = (int*)c.take(sizeof(int) * (size_t)N * (size_t)P);
+  l.rank = (int*)c.take(sizeof(int) * (size_t)N * (size_t)P);
+  l.grid = c.take(grid ? grid_carve(nullptr, nullptr, N, P, P, kClusterCellTarget) : 0);
+  l.bytes = c.off;
+  return l;
+}
+
+}  // namespace pointops
+
+using namespace pointops;
+
+extern "C" size_t pointops_cluster_workspace_bytes(int64_t N, int64_t P) {
+  if (!cluster_shape_ok(N, P, 3) || N == 0) return 0;
+  return cluster_layout(nullptr, N, P, cluster_uses_grid(N, P)).bytes;
+}
+
+extern "C" int pointops_cluster_dbscan(const float* points, const int64_t* lengths, int64_t N, int64_t P, int64_t D,
+                                       float eps, int64_t min_points, int64_t* labels, int64_t* num_clusters,
+                                       uint8_t* core_mask, void* workspace, size_t workspace_bytes, void* stream_) {
+  POINTOPS_REQUIRE(cluster_shape_ok(N, P, D), "cluster_dbscan: need 0 <= N < 65536, 0 <= P < 2^30 and 1 <= D <= 3");
+  POINTOPS_REQUIRE(eps > 0.0f && eps <= FLT_MAX && min_points >= 1,
+                   "cluster_dbscan: need a finite eps > 0 and min_points >= 1");
+  if (N == 0) return POINTOPS_OK;
+  const bool grid = cluster_uses_grid(N, P);
+  const ClusterLayout l = cluster_layout(workspace, N, P, grid);
+  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
+    set_error("cluster_dbscan: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
+    return POINTOPS_EWORKSPACE;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  hipLaunchKernelGGL(cluster_lengths_kernel, dim3((unsigned)ceil_div(N, kClBlock)), dim3(kClBlock), 0, stream, lengths,
+                     (int)N, (int)P, l.len);
+  ClusterView v{};
+  v.points = points;
+  v.len = l.len;
+  v.P = (int)P;
+  v.r2 = eps * eps;  // fp32 product, as ball query's radius2
+  if (grid) {
+    GridWs ws;
+    grid_carve(&ws, l.grid, N, P, P, kClusterCellTarget);
+    // K = 0: the build's padding of search rows has nothing to write
+    const KnnArgs a = make_knn_args(points, points, l.len, l.len, N, P, P, D, 0, 0, nullptr, nullptr, stream);
+    GridBuild b{};
+    b.c_target = kClusterCellTarget;
+    b.h_min = eps * 1.001f;
+    b.same = true;
+    b.refine = -1;
+    const int rc = grid_build(a, ws, b);
+    if (rc != POINTOPS_OK) return rc;
+    v.clouds = ws.cloud;
+    v.edges = ws.edges;
+    v.cell_start = ws.cell_start;
+    v.sorted = ws.sorted;
+    v.cell_cap = ws.cell_cap;
+  }
+  const int minp = (int)(min_points > INT_MAX ? INT_MAX : min_points);
+  if (P > 0) {
+    const dim3 pgrid((unsigned)ceil_div(P, kClBlock), (unsigned)N);
+    with_exact<3>(Ints<1, 2, 3>{}, (int)D, [&](auto DT) {
+      hipLaunchKernelGGL((cluster_count_kernel<DT>), pgrid, dim3(kClBlock), 0, stream, v, minp, core_mask, l.parent);
+      hipLaunchKernelGGL((cluster_union_kernel<DT>), pgrid, dim3(kClBlock), 0, stream, v, (const uint8_t*)core_mask,
+                         l.parent);
+      hipLaunchKernelGGL((cluster_flatten_kernel<DT>), pgrid, dim3(kClBlock), 0, stream, v, (const uint8_t*)core_mask,
+                         l.parent, labels);
+    });
+  }
+  hipLaunchKernelGGL(cluster_scan_kernel, dim3((unsigned)N), dim3(kClScanBlock), 0, stream, (const int64_t*)l.len, (int)P,
+                     (const int64_t*)labels, l.rank, num_clusters);
+  if (P > 0)
+    hipLaunchKernelGGL(cluster_relabel_kernel, dim3((unsigned)ceil_div(P, kClBlock), (unsigned)N), dim3(kClBlock), 0,
+                       stream, (const int64_t*)l.len, (int)P, (const int*)l.rank, labels);
+  return check_launch("cluster_dbscan");
+}

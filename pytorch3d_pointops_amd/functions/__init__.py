@@ -2,6 +2,7 @@
 (chamfer_distance and sample_pdf are imported by module path there too)."""
 from .. import ops as _ops  # noqa: F401  registers torch.ops.pointops_amd.* (torch.compile traces through them)
 from .ball_query import ball_query
+from .cluster import DBSCANClusters, cluster_dbscan, euclidean_clusters
 from .fpfh import fpfh_features, mutual_nearest_neighbors, point_pair_features
 from .knn import knn_gather, knn_points
 from .packed_to_padded import packed_to_padded, padded_to_packed

@@ -219,6 +219,13 @@ class Pointclouds:
                 self._feature_names.append("normals")
         return normals
 
+    def cluster_dbscan(self, eps: float, min_points: int = 10):
+        """DBSCANClusters(labels (N, max P_n) int64, num_clusters (N,), core_mask (N, max P_n) bool) of every cloud
+        (functions.cluster_dbscan): label -1 on noise and on padding rows."""
+        from ..functions.cluster import cluster_dbscan
+
+        return cluster_dbscan(self, eps, min_points)
+
     # ------------------------------------------------------------------ single clouds, copies of clouds
     def get_cloud(self, index: int):
         """(points (P, 3), {name: (P, C)}) of one cloud (reference :938)."""
