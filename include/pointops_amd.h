@@ -489,6 +489,65 @@ int pointops_cluster_dbscan(const float* points, const int64_t* lengths, int64_t
                             int64_t min_points, int64_t* labels, int64_t* num_clusters, uint8_t* core_mask,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * RANSAC plane extraction: the dominant plane of every cloud (floor, road, table, wall) -- Open3D's segment_plane,
+ * PCL's SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE -- device half of functions/plane.py.  The
+ * semantics are this library's own; all fp32 and fp64 arithmetic is unfused and in the order written.  float32 points,
+ * three dimensions.  A plane is (a, b, c, d): the points with a x + b y + c z + d = 0, (a, b, c) a unit normal.
+ *   points (N,P,3) fp32; lengths (N,) or NULL (= P; clamped into [0,P]); mask (N,P) one byte per row or NULL;
+ *   samples_in (N,H,3) int64 or NULL.
+ *   1. Valid rows: row i of cloud n is VALID when i < lengths[n] and mask is NULL or mask[n,i] != 0.  The valid rows in
+ *      ascending order are v[0..M_n).
+ *   2. Draws (samples_in == NULL and M_n >= 3): hypothesis h takes the rows v[i0], v[i1], v[i2] with (i0, i1, i2) the
+ *      three distinct positions of pointops_ransac_alignment's step 2 -- the same hash32(seed, first_cloud + n, h, j),
+ *      the same mulhi reductions -- for M = M_n.  first_cloud is the index of cloud 0 of this call in the caller's
+ *      batch, so a batch cut into several calls draws what one call would.  With samples_in the triple is
+ *      samples_in[n,h,:], rows of the cloud, and nothing is drawn.
+ *   3. A hypothesis is INVALID when M_n < 3 (without samples_in), when one of its rows is not valid or two are the same
+ *      (only samples_in can do that), or when it fails a test of step 4.
+ *   4. The plane of a hypothesis, in fp64 on the three fp32 points p0, p1, p2:  e1 = p1 - p0, e2 = p2 - p0,
+ *      c = e1 x e2 with c0 = e1[1]*e2[2] - e1[2]*e2[1], c1 = e1[2]*e2[0] - e1[0]*e2[2], c2 = e1[0]*e2[1] - e1[1]*e2[0];
+ *      |v|^2 = (v0*v0 + v1*v1) + v2*v2.  It is invalid unless |c|^2 > (1e-12 * |e1|^2) * |e2|^2 (collinear and
+ *      coincident points and NaN fail this) and, with use_axis, unless (c.A)^2 >= (cosm * cosm) * |c|^2, where
+ *      c.A = (c0*A0 + c1*A1) + c2*A2, A = (axis_x, axis_y, axis_z) and cosm = cos_max_angle, both fp32 widened to fp64:
+ *      the normal lies within max_angle of +-A.  The caller passes A with unit length.  Then n = c / sqrt(|c|^2),
+ *      d = -((n0*p0[0] + n1*p0[1]) + n2*p0[2]).  Sign: with use_axis, (n, d) is negated when n.A < 0; without, when the
+ *      component of n of largest magnitude (the lowest index among equal magnitudes) is negative.  (n, d) is rounded
+ *      once to fp32; a d that is not finite in fp32 makes the hypothesis invalid.  An invalid hypothesis has the plane
+ *      (0,0,0,0) and the count -1.
+ *   5. Residual of a row (x, y, z) under a plane:  r = ((x*a + y*b) + z*c) + d in fp32; the row is an inlier iff
+ *      |r| <= distance_threshold.  The count of a valid hypothesis is the number of inliers among the valid rows (int32).
+ *   6. best[n] = the valid hypothesis with the largest count, the lowest index among equals; -1 when none is valid.
+ *   7. Evaluation of a plane: the same formulas give the mask over all P rows (0 for rows that are not valid), the count
+ *      and rmse = sqrt(sum over the inliers of r*r / max(count, 1)), r*r and the sum in fp64, by block partials in a
+ *      fixed order.
+ *   8. The winner is evaluated; then, refine_steps times, per cloud and on the device: with the pivot v[0]'s point and
+ *      q = p - pivot (fp64), the moments S1 = count, Sq = sum q, Sqq = sum q q^T over the current inliers (fp64 block
+ *      partials in a fixed order); centroid m = Sq / S1, covariance Sqq / S1 - m m^T; the eigenvector n of its smallest
+ *      eigenvalue (cyclic Jacobi in fp64: sym3_eigen_f64 of csrc/small_solvers.h), d = -n.(pivot + m), the sign rule
+ *      of step 4, one rounding to fp32.  The fit is evaluated and accepted (plane, mask, count, rmse) iff its count >=
+ *      the current count; else the cloud keeps what it has and ignores the later steps.  A fit from fewer than three
+ *      inliers, a fit that is not finite and -- with use_axis -- a fit outside the cone are rejected likewise.
+ *   9. best[n] == -1 gives the plane (0,0,0,0), an all-zero mask, num_inliers 0 and rmse 0.
+ *   Outputs: planes (N,4) fp32, inlier_mask (N,P) one byte 0/1 per row, num_inliers (N,) int64, rmse (N,) fp32, best
+ *   (N,) int64; optional (NULL skips them) counts (N,H) int32, hyp_planes (N,H,4) fp32 and samples_out (N,H,3) int64:
+ *   the rows of every triple (-1 where nothing was drawn).  Every output is fully written, P == 0 included.  No
+ *   atomics, nothing synchronises, nothing is read back: results are bit-reproducible.
+ *   workspace: pointops_plane_workspace_bytes(N, P, H); a short or null one is POINTOPS_EWORKSPACE with nothing written.
+ *   0 <= N < 65536 (a bigger batch goes in slices with first_cloud), P <= 65535 * pointops_plane_chunk(),
+ *   1 <= H <= 2^24, distance_threshold finite and >= 0, refine_steps >= 0, first_cloud >= 0 and, with use_axis, a unit
+ *   axis and 0 <= cos_max_angle <= 1: anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing.
+ *   pointops_plane_chunk(): the number of records one scoring workgroup walks (the sizes around which tests probe).
+ */
+int64_t pointops_plane_chunk(void);
+size_t pointops_plane_workspace_bytes(int64_t N, int64_t P, int64_t H);
+int pointops_segment_plane(const float* points, const int64_t* lengths, const uint8_t* mask, const int64_t* samples_in,
+                           int64_t N, int64_t P, int64_t H, int64_t seed, int64_t first_cloud,
+                           float distance_threshold, int use_axis, float axis_x, float axis_y, float axis_z,
+                           float cos_max_angle, int refine_steps, float* planes, uint8_t* inlier_mask,
+                           int64_t* num_inliers, float* rmse, int64_t* best, int32_t* counts, float* hyp_planes,
+                           int64_t* samples_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

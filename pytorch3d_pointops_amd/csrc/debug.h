@@ -23,6 +23,8 @@
 //   fps_mode=0|1|2     FPS clusters: round-robin members / XCD-local members / XCD-local + L2 exchange
 //   fps_spin_limit=N   FPS exchange spin bound (tests force the timeout repair path with 0)
 //   ransac_lds=1       RANSAC scoring: the records through an LDS tile instead of the scalar path (ransac.hip)
+//   plane_lds=0|1      segment_plane scoring: the records through the scalar path / through an LDS tile (plane.hip; default 1)
+//   plane_hpl=1|2      segment_plane scoring: hypotheses per lane (default: 2 above 256 hypotheses)
 //   cluster_grid=0|1   cluster_dbscan: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 #pragma once
 

@@ -28,12 +28,11 @@
 #include "common.h"
 #include "debug.h"
 #include "ransac_hypothesis.h"
+#include "ransac_select.h"
 #include "wave.h"
 
 namespace pointops {
 
-constexpr int kRsBlock = 256;
-constexpr int kRsWaves = kRsBlock / kWave;
 constexpr int kRansacChunk = 256;  // records per scoring block (exported: pointops_ransac_chunk)
 constexpr int kRsPairRows = 8;     // consecutive rows per thread of the compaction
 constexpr int kRsPairTile = kRsBlock * kRsPairRows;  // rows per step of the compaction (2048)
@@ -53,12 +52,6 @@ inline int64_t rs_pair_tiles(int64_t P) { return P > 0 ? ceil_div(P, (int64_t)kR
 inline int rs_eval_blocks(int64_t P) {
   const int64_t nb = ceil_div(P, (int64_t)kRsBlock * kRsRowsPerThread);
   return (int)(nb < 1 ? 1 : (nb > kRsMaxBlocks ? kRsMaxBlocks : nb));
-}
-
-__device__ __forceinline__ int rs_length(const int64_t* __restrict__ lengths, int n, int P) {
-  if (lengths == nullptr) return P;
-  const int64_t l = lengths[n];
-  return (int)(l < 0 ? 0 : (l > P ? P : l));
 }
 
 // the row of Y that row i of X is matched to, or -1 when the row is no valid correspondence
@@ -258,22 +251,6 @@ __global__ __launch_bounds__(kRsBlock) void ransac_score_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------- 4. selection
-// The largest key of the workgroup, valid in thread 0.  s_key: kRsWaves words of LDS.
-__device__ __forceinline__ unsigned long long rs_block_max(unsigned long long key, unsigned long long* s_key) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(key, off, kWave);
-    key = o > key ? o : key;
-  }
-  if ((threadIdx.x & (kWave - 1)) == 0) s_key[threadIdx.x / kWave] = key;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kRsWaves; ++w) key = s_key[w] > key ? s_key[w] : key;
-  }
-  return key;
-}
-
 // One lane per (cloud, hypothesis): the sum of its chunk partials (coalesced over the hypotheses), the optional
 // `counts` output, and the tile's largest key -- count in the high word, the inverted index in the low one, so that
 // the maximum is the largest count at the lowest index; 0 = no valid hypothesis (a valid one has a low word >= 1).

@@ -1,7 +1,7 @@
 // small_solvers.h -- the per-lane 3x3 / 2x2 solvers of local_frames.hip and points_alignment.hip, __host__ __device__.
 //
 //   sym3_eigen     cyclic Jacobi in fp64 on a symmetric fp32 3x3 matrix: ascending eigenvalues, eigenvectors as columns,
-//                  rounded to fp32 (local_frames_kernel).
+//                  rounded to fp32 (local_frames_kernel); sym3_eigen_f64 is its fp64-in, fp64-out core (plane refits).
 //   pa_svd<D>      one-sided Jacobi SVD of a d x d fp64 matrix, U completed by orthogonality where a singular value is
 //                  negligible; pa_solve<D> turns the reduced alignment moments into R, T, s (alignment_solve_kernel).
 //
@@ -57,16 +57,13 @@ __host__ __device__ __forceinline__ void eig_order(double (&l)[3], double (&v)[3
   }
 }
 
-// Eigen-decomposition of the symmetric fp32 matrix c: ascending eigenvalues lam, eigenvectors as columns of vec.
-__host__ __device__ __forceinline__ void sym3_eigen(const float (&c)[3][3], float (&lam)[3], float (&vec)[3][3]) {
-  double a[3][3], v[3][3];
+// The fp64 core: cyclic Jacobi on the symmetric matrix a (destroyed), then the stable ordering.  Ascending eigenvalues
+// l, eigenvectors as columns of v.  (segment_plane's refit calls it on an fp64 covariance: plane_hypothesis.h.)
+__host__ __device__ __forceinline__ void sym3_eigen_f64(double (&a)[3][3], double (&l)[3], double (&v)[3][3]) {
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      a[r][q] = (double)c[r][q];
-      v[r][q] = r == q ? 1.0 : 0.0;
-    }
+    for (int q = 0; q < 3; ++q) v[r][q] = r == q ? 1.0 : 0.0;
   for (int sweep = 0; sweep < kJacobiMaxSweeps; ++sweep) {
     const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
     const double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
@@ -75,10 +72,22 @@ __host__ __device__ __forceinline__ void sym3_eigen(const float (&c)[3][3], floa
     jacobi_rotate<0, 2>(a, v);
     jacobi_rotate<1, 2>(a, v);
   }
-  double l[3] = {a[0][0], a[1][1], a[2][2]};
+  l[0] = a[0][0];
+  l[1] = a[1][1];
+  l[2] = a[2][2];
   eig_order<0, 1>(l, v);
   eig_order<1, 2>(l, v);
   eig_order<0, 1>(l, v);
+}
+
+// Eigen-decomposition of the symmetric fp32 matrix c: ascending eigenvalues lam, eigenvectors as columns of vec.
+__host__ __device__ __forceinline__ void sym3_eigen(const float (&c)[3][3], float (&lam)[3], float (&vec)[3][3]) {
+  double a[3][3], l[3], v[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) a[r][q] = (double)c[r][q];
+  sym3_eigen_f64(a, l, v);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     lam[r] = (float)l[r];

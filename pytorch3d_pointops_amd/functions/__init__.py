@@ -8,6 +8,7 @@ from .knn import knn_gather, knn_points
 from .packed_to_padded import packed_to_padded, padded_to_packed
 from .points_alignment import (ICPSolution, SimilarityTransform, corresponding_points_alignment,
                                iterative_closest_point)
+from .plane import PlaneSegmentation, PlaneSet, segment_plane, segment_planes
 from .points_normals import estimate_pointcloud_local_coord_frames, estimate_pointcloud_normals
 from .ransac import RansacSolution, ransac_alignment
 from .sample_farthest_points import sample_farthest_points

@@ -226,6 +226,13 @@ class Pointclouds:
 
         return cluster_dbscan(self, eps, min_points)
 
+    def segment_plane(self, **kwargs):
+        """PlaneSegmentation(planes (N, 4), inliers (N, max P_n) bool, num_inliers (N,), rmse (N,), best (N,), ...) of
+        every cloud (functions.segment_plane, same keywords): the dominant plane, padding rows never inliers."""
+        from ..functions.plane import segment_plane
+
+        return segment_plane(self, **kwargs)
+
     # ------------------------------------------------------------------ single clouds, copies of clouds
     def get_cloud(self, index: int):
         """(points (P, 3), {name: (P, C)}) of one cloud (reference :938)."""
