@@ -9,11 +9,15 @@
 //   grid_long_box=0|1  K in (32, 64]: uncertified queries to the wave search / to the box search (default: by query count)
 //   grid_refine=0      no refined cells (over-full neighbourhoods still go to the box search, over whole cells)
 //   grid_same=0        do not reuse the point sort as the query order when p1 is p2
-//   grid_c_scale=F     multiply the grid KNN's points-per-cell target (sweeps)
+//   grid_c_scale=F     multiply the grid KNN's points-per-cell target (the target stays floored at 1 point per cell);
+//                      tested bit for bit over F in [1/64, 1e6] (tests/test_grid_cell_size_gpu.py)
+//   grid_big=1         grid KNN: the run words of the biggest clouds (runs of up to 255 records) whatever the cloud size
 //   ball_small=0|1     ball query, few queries: never / always the wave-per-query kernel (ball_small.hip; default: by shape)
 //   ball_grid=0|1      ball query: never / whenever possible through the grid (default: by shape)
 //   ball_factor=F      ball query: grid-or-scan crossover constant
 //   ball_order=0       ball query: scan-mode clouds keep their queries in storage order (no coarse-cell order)
+//   ball_stage=0       ball query: listed clouds write their hits straight to the rows instead of staging them in LDS
+//   spfh_lanes=1|8     SPFH: one lane per point / eight lanes striding over its neighbours (default: 8 from K = 8 on)
 //   knn_bwd_mode=a|t   knn backward grad_p2: device atomics / LDS tiles;  knn_bwd_split=S
 //   gather_bwd_mode=a|t, gather_bwd_split=S   the same for knn_gather's backward
 //   chamfer_overlap=0  one-call chamfer: the reverse search on the caller's stream instead of a side stream

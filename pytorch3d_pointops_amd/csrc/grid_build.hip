@@ -228,7 +228,11 @@ __global__ __launch_bounds__(kSetupBlock) void grid_setup_kernel(
     }
     float inv_h = 1.0f;
     int G[3] = {1, 1, 1};
-    if (ok && any_active) {
+    // A cloud of at most c_target points is ONE cell.  (For a target of one cell the sizing loop above ends with h = the
+    // largest extent e, and e * (1 / e) rounds to 1 for most e: that dimension -- all three when the extents are equal --
+    // used to get a second cell for nothing but the points on the box's upper face.)
+    const bool one_cell = (float)len2 <= c_target;
+    if (ok && any_active && !one_cell) {
       // at most kGMax cells per dimension: a long 1-D cloud would otherwise clamp nearly all of its points into the
       // last cell (exact, but one cell = the whole cloud)
       for (int d = 0; d < 3; ++d)
@@ -810,7 +814,13 @@ size_t grid_carve(GridWs* ws, char* base, int64_t N, int64_t P1, int64_t P2, flo
   w.grid_flag = (int*)cv.take(sizeof(int) * (size_t)N);
   w.qtmp = (float4*)cv.take(sizeof(float4) * (size_t)N * (size_t)P1);
   w.rdesc_cap = (int)(P2 / 64 + 1);  // a refined cell holds more than refine_threshold() >= 64 points
-  w.pool_cap = (int)(4 * P2 + 64);   // sum of (s^3 + 1) <= sum of (8 count / c + 9) over refined cells
+  // Tables of the refined cells: s^3 + 1 ints each, s = ceil(cbrt(x)) for x = count / c.  A refined cell holds more than
+  // refine_threshold(c) = max(64, 28 c) points, so x > 28 for every c >= 1 (the KNN target's floor), cbrt(x) > 3 and
+  // s^3 < x (1 + 1 / 3)^3 < 2.4 x (the cap s <= kRefineMaxS only lowers it): the tables of a cloud sum to less than
+  // 2.4 P2 / c + P2 / 64 <= 2.5 P2, inside the pool for every c >= 1.  For c < 1 (no caller asks for it) the bound grows
+  // as 1 / c and the pool can run out: the scan pass then hands the cell a descriptor without a table (`fits`, count 0),
+  // the cell stays unrefined and the box search walks it whole -- slower, never wrong, never out of bounds.
+  w.pool_cap = (int)(4 * P2 + 64);
   w.refine_ref = (int*)cv.take(sizeof(int) * (size_t)N * cap);
   w.rdesc = (RefinedCell*)cv.take(sizeof(RefinedCell) * (size_t)N * (size_t)w.rdesc_cap);
   w.rcount = (int*)cv.take(sizeof(int) * (size_t)N);
