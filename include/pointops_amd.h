@@ -490,6 +490,44 @@ int pointops_cluster_dbscan(const float* points, const int64_t* lengths, int64_t
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * ISS keypoints (Intrinsic Shape Signatures, Zhong 2009; Open3D's compute_iss_keypoints, PCL's ISSKeypoint3D with the
+ * unweighted scatter matrix): which points of a cloud deserve a descriptor -- device half of functions/iss.py.  The
+ * semantics are this library's own; all fp32 and fp64 arithmetic is unfused and in the order written.  Every output is a
+ * function of the input alone: the scatter matrix is summed in integers, so the order of the walk never shows.
+ *   points (N,P,3) fp32; lengths (N,) or NULL (= P; clamped into [0,P]); rs = salient_radius, rn = non_max_radius.
+ *   d2(i,j) = (dx*dx + dy*dy) + dz*dz in fp32, dx = x_i - x_j: ball query's and cluster_dbscan's expression.  For every
+ *   row i < lengths[n] of cloud n:
+ *   1. SUPPORT.  S_i = { j < lengths[n] : d2(i,j) < fl32(rs * rs) }; i itself is in S_i when its coordinates are
+ *      finite.  n_i = |S_i|.
+ *   2. INTEGER MOMENTS.  e = the smallest integer with fl32(rs) <= 2^e, s = 2^(19 - e) as a double.  Per coordinate
+ *      q = rint(((double)x_j - (double)x_i) * s), round half to even, an integer with |q| <= 2^19 up to rounding.
+ *      M1 = sum over S_i of q (x, y, z), M2 = sum of q q^T (xx, xy, xz, yy, yz, zz), in int64: with P <= 2^24 no sum
+ *      reaches 2^63.
+ *   3. COVARIANCE in fp64:  m_a = (double)M1_a / n_i;  C_ab = ((double)M2_ab / n_i - m_a * m_b) * s^-2.  n_i == 0: C = 0.
+ *   4. EIGENVALUES.  sym3_eigen_f64(C) of csrc/small_solvers.h (cyclic Jacobi in fp64), ascending, each rounded once
+ *      to fp32: eigenvalues[n,i,:] = (l0, l1, l2).
+ *   5. SALIENCY in fp32, from the rounded eigenvalues:  saliency = l0 when  l0 > 2^-20 * l2  and  l1 < gamma_21 * l2  and
+ *      l0 < gamma_32 * l1,  else 0.  The first test is the floor: an eigenvalue below the resolution of the integer
+ *      moments is rounding, not structure (it also covers supports of fewer than four points).  The other two are
+ *      Open3D's quotient tests written as products: no division by zero.
+ *   6. NON-MAXIMUM SUPPRESSION.  T_i = { j < lengths[n] : d2(i,j) < fl32(rn * rn) }.  mask[n,i] = 1 iff saliency_i > 0
+ *      and |T_i| >= min_neighbors and no j in T_i beats i, where j BEATS i when saliency_j > saliency_i, or
+ *      saliency_j == saliency_i and j < i (ties to the lower index; Open3D keeps both ends of an exact tie).
+ *   Rows at or past the length: eigenvalues 0, saliency 0, mask 0 (moments 0).
+ *   Outputs: eigenvalues (N,P,3) fp32, saliency (N,P) fp32, mask (N,P) one byte 0/1 per row; optional (NULL skips it)
+ *   moments (N,P,10) int64 = (n_i, M1[3], M2[6]).  Every output is fully written.  No atomics of its own, nothing
+ *   synchronises, nothing is read back: results are bit-reproducible.
+ *   workspace: pointops_iss_workspace_bytes(N, P); a short or null one is POINTOPS_EWORKSPACE with nothing written.
+ *   0 <= N < 65536 (a bigger batch goes in slices), 0 <= P <= 2^24, both radii and both gammas finite and > 0,
+ *   min_neighbors >= 0: anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing.
+ */
+size_t pointops_iss_workspace_bytes(int64_t N, int64_t P);
+int pointops_iss_keypoints(const float* points, const int64_t* lengths, int64_t N, int64_t P, float salient_radius,
+                           float non_max_radius, float gamma_21, float gamma_32, int64_t min_neighbors,
+                           float* eigenvalues, float* saliency, uint8_t* mask, int64_t* moments, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/*
  * RANSAC plane extraction: the dominant plane of every cloud (floor, road, table, wall) -- Open3D's segment_plane,
  * PCL's SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE -- device half of functions/plane.py.  The
  * semantics are this library's own; all fp32 and fp64 arithmetic is unfused and in the order written.  float32 points,

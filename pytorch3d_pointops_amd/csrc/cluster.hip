@@ -15,131 +15,22 @@
 //             the roots it reads are final only once every hook of the union launch has been made.
 //   scan      one workgroup per cloud: the roots (label == own index) ranked in index order -> rank[], num_clusters
 //   relabel   label = rank[root]
-// A WALK is ball_grid_lane_kernel's: the nine x-runs of the 3x3x3 cube around the lane's cell, taken only under that
-// kernel's certificate `whole || box_lower_bound<2>(...) >= r2` (every unvisited point has dist2 >= r2).  A lane without
-// the certificate, and every lane of a cloud whose grid was refused (non-finite coordinates, cell caps) or that is too
-// small for one, walks the raw cloud instead: all pairs, the same comparison, so which path a lane takes depends on
-// the input alone and never changes a result.  POINTOPS_DEBUG=cluster_grid=0 sends every cloud that way.
+// A WALK is radius_walk.h's (shared with iss.hip): the 3x3x3 cube around the lane's cell under ball query's certificate,
+// else the raw cloud by all pairs with the same comparison, so which path a lane takes depends on the input alone and
+// never changes a result.  POINTOPS_DEBUG=cluster_grid=0 sends every cloud by all pairs.
 #include <limits.h>
 
 #include "cluster_union.h"
 #include "debug.h"
 #include "grid.h"
+#include "radius_walk.h"
 #include "wave.h"
 
 namespace pointops {
 
-constexpr int kClBlock = 256;
 constexpr int kClScanBlock = 1024;
 constexpr float kClusterCellTarget = 2.0f;    // density floor of the cell size (ball query's); eps usually decides
 constexpr int kClusterGridMinPoints = 512;    // smaller clouds: all pairs (the build's fixed passes cost more)
-
-struct ClusterView {
-  const float* points;       // (N, P, D)
-  const int64_t* len;        // (N,) clamped
-  const GridCloud* clouds;   // grid state: null when the call builds no grid
-  const float* edges;
-  const int* cell_start;
-  const float4* sorted;
-  int cell_cap, P;
-  float r2;
-};
-
-template <int D>
-struct ClusterLane {
-  int i;            // the point's index in its cloud
-  float x, y, z;
-  bool cube;        // walk the 3x3x3 cube (certified); else the raw cloud
-  int cy, cz, X0, X1;
-};
-
-// lane t of cloud n: position t of the cell order where the cloud has a grid, point t where it has none
-template <int D>
-__device__ __forceinline__ ClusterLane<D> cluster_lane(const ClusterView& v, const GridCloud& g, bool grid, int n,
-                                                       int t) {
-  ClusterLane<D> L;
-  L.cy = L.cz = L.X0 = L.X1 = 0;
-  if (grid) {
-    const float4 q = v.sorted[(int64_t)n * (v.P + kSortedPad) + t];
-    L.x = q.x, L.y = q.y, L.z = q.z;
-    L.i = __float_as_int(q.w);
-    int cx;
-    point_cells(g, L.x, L.y, L.z, cx, L.cy, L.cz);
-    L.X0 = max(cx - 1, 0), L.X1 = min(cx + 1, g.G[0] - 1);
-    const int Y0 = max(L.cy - 1, 0), Y1 = min(L.cy + 1, g.G[1] - 1);
-    const int Z0 = max(L.cz - 1, 0), Z1 = min(L.cz + 1, g.G[2] - 1);
-    bool whole;
-    const float lb = box_lower_bound<2>(g, v.edges + (int64_t)n * 3 * kEdgeStride, L.x, L.y, L.z, L.X0, L.X1, Y0, Y1,
-                                        Z0, Z1, whole);
-    L.cube = whole || lb >= v.r2;  // every unvisited point has computed dist2 >= lb
-  } else {
-    load_point3<D>(v.points + ((int64_t)n * v.P + t) * D, L.x, L.y, L.z);
-    L.i = t;
-    L.cube = false;
-  }
-  return L;
-}
-
-// fn(j) for every neighbour j of the lane (dist2 < r2, the lane itself included), until fn returns false
-template <int D, typename Fn>
-__device__ __forceinline__ void cluster_walk(const ClusterView& v, const GridCloud& g, const ClusterLane<D>& L, int n,
-                                             int len, Fn fn) {
-  if (L.cube) {
-    const float4* __restrict__ sp = v.sorted + (int64_t)n * (v.P + kSortedPad);
-    const int* __restrict__ cstart = v.cell_start + (int64_t)n * (v.cell_cap + 1);
-    for (int dz = -1; dz <= 1; ++dz) {
-      const int z = L.cz + dz;
-      if (z < 0 || z >= g.G[2]) continue;
-      for (int dy = -1; dy <= 1; ++dy) {
-        const int y = L.cy + dy;
-        if (y < 0 || y >= g.G[1]) continue;
-        const int rowbase = (z * g.G[1] + y) * g.G[0];
-        const int s = cstart[rowbase + L.X0], e = cstart[rowbase + L.X1 + 1];
-        for (int k = s; k < e; ++k) {
-          const float4 c = sp[k];
-          if (point_dist<D, 2>(L.x, L.y, L.z, c) < v.r2) {
-            if (!fn(__float_as_int(c.w))) return;
-          }
-        }
-      }
-    }
-  } else {
-    const float* __restrict__ pts = v.points + (int64_t)n * v.P * D;
-    for (int j = 0; j < len; ++j) {
-      float4 c;
-      load_point3<D>(pts + (int64_t)j * D, c.x, c.y, c.z);
-      if (point_dist<D, 2>(L.x, L.y, L.z, c) < v.r2) {
-        if (!fn(j)) return;
-      }
-    }
-  }
-}
-
-// (cloud, lane, length, grid state) of a thread of the per-point launches; false: nothing to walk
-struct ClusterItem {
-  int n, t, len;
-  bool grid;
-};
-__device__ __forceinline__ ClusterItem cluster_item(const ClusterView& v, GridCloud& g) {
-  ClusterItem it;
-  it.n = blockIdx.y;
-  it.t = blockIdx.x * kClBlock + threadIdx.x;
-  it.len = (int)v.len[it.n];
-  it.grid = false;
-  if (v.clouds != nullptr) {
-    g = v.clouds[it.n];
-    it.grid = g.use_grid != 0;
-  }
-  return it;
-}
-
-__global__ __launch_bounds__(kClBlock) void cluster_lengths_kernel(const int64_t* __restrict__ lengths, int N, int P,
-                                                                 int64_t* __restrict__ len) {
-  const int n = blockIdx.x * kClBlock + threadIdx.x;
-  if (n >= N) return;
-  const int64_t l = lengths != nullptr ? lengths[n] : (int64_t)P;
-  len[n] = l < 0 ? 0 : (l > P ? P : l);
-}
 
 template <int D>
 __global__ __launch_bounds__(kClBlock) void cluster_count_kernel(ClusterView v, int min_points,

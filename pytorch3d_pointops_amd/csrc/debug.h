@@ -30,6 +30,7 @@
 //   plane_lds=0|1      segment_plane scoring: the records through the scalar path / through an LDS tile (plane.hip; default 1)
 //   plane_hpl=1|2      segment_plane scoring: hypotheses per lane (default: 2 above 256 hypotheses)
 //   cluster_grid=0|1   cluster_dbscan: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
+//   iss_grid=0|1       iss_keypoints: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 #pragma once
 
 namespace pointops {

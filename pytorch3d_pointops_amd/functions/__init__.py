@@ -4,6 +4,7 @@ from .. import ops as _ops  # noqa: F401  registers torch.ops.pointops_amd.* (to
 from .ball_query import ball_query
 from .cluster import DBSCANClusters, cluster_dbscan, euclidean_clusters
 from .fpfh import fpfh_features, mutual_nearest_neighbors, point_pair_features
+from .iss import ISSKeypoints, cloud_resolution, iss_keypoints, keypoints_to_padded
 from .knn import knn_gather, knn_points
 from .packed_to_padded import packed_to_padded, padded_to_packed
 from .points_alignment import (ICPSolution, SimilarityTransform, corresponding_points_alignment,

@@ -226,6 +226,13 @@ class Pointclouds:
 
         return cluster_dbscan(self, eps, min_points)
 
+    def iss_keypoints(self, **kwargs):
+        """ISSKeypoints(mask (N, max P_n) bool, saliency (N, max P_n), eigenvalues (N, max P_n, 3), num_keypoints (N,))
+        of every cloud (functions.iss_keypoints, same keywords): padding rows are never keypoints."""
+        from ..functions.iss import iss_keypoints
+
+        return iss_keypoints(self, **kwargs)
+
     def segment_plane(self, **kwargs):
         """PlaneSegmentation(planes (N, 4), inliers (N, max P_n) bool, num_inliers (N,), rmse (N,), best (N,), ...) of
         every cloud (functions.segment_plane, same keywords): the dominant plane, padding rows never inliers."""
