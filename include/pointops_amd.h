@@ -586,6 +586,52 @@ int pointops_segment_plane(const float* points, const int64_t* lengths, const ui
                            int64_t* num_inliers, float* rmse, int64_t* best, int32_t* counts, float* hyp_planes,
                            int64_t* samples_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Voxel-grid pooling (Open3D's voxel_down_sample, PCL's VoxelGrid, the grid pooling of point networks): one point --
+ * the centroid -- and one mean feature per occupied voxel, and the integer cell coordinates sparse convolutions consume
+ * -- device half of functions/voxel.py.  The semantics are this library's own; all fp64 arithmetic is unfused and in the
+ * order written.  Every output is a function of the input alone and has the static shape of the input.
+ *   points (N,P,3) fp32; lengths (N,) or NULL (= P; clamped into [0,P]); v = voxel_size, finite in fp32 and > 0;
+ *   features (N,P,C) fp32 or NULL (C == 0); origin NULL, (3,) (origin_per_cloud == 0) or (N,3) (origin_per_cloud != 0).
+ *   1. LIVE ROWS.  Row i of cloud n is live when i < lengths[n] and its three coordinates are finite.  Every other row
+ *      belongs to no voxel.
+ *   2. ORIGIN per cloud and axis a, in fp64.  With an origin: o_a = (double)origin_a.  Without: Open3D's rule
+ *      o_a = (double)min_a - 0.5 * (double)v, min_a the fp32 minimum over the cloud's live rows.
+ *   3. CELL.  c_a(x) = floor(((double)x - o_a) / (double)v): a division, monotone in x.
+ *   4. EXTENT.  c_lo = c_a(min_a), c_hi = c_a(max_a).  The cloud is REFUSED, status[n] = 1, when on any axis
+ *      c_hi - c_lo >= 2^21, or |c_lo| >= 2^31, or |c_hi| >= 2^31 (fp64 comparisons, before any conversion to an integer;
+ *      a comparison with a NaN -- a non-finite origin -- refuses).  A refused cloud has no voxels.  Every other cloud,
+ *      one without a live row included, has status[n] = 0.
+ *   5. VOXELS.  The voxels of a cloud are the distinct cells (c_x, c_y, c_z) of its live rows, numbered 0 .. V-1 in
+ *      ascending (c_z, c_y, c_x) order; the members of a voxel are taken in ascending row index.
+ *   6. OUTPUTS, padded to P voxel rows; rows >= V, and every row of a refused or empty cloud, hold the fill value.
+ *        num_voxels  (N,)     int64  V                                            --
+ *        status      (N,)     int32  0, or 1 for a refused cloud                  --
+ *        inverse     (N,P)    int64  the voxel of every input row                 -1 (rows that are not live, refused clouds)
+ *        counts      (N,P)    int64  members per voxel                            0
+ *        first_index (N,P)    int64  the lowest member row of every voxel         -1
+ *        coords      (N,P,3)  int64  (c_x, c_y, c_z), relative to the origin      0      (NULL skips it)
+ *        centroids   (N,P,3)  fp32   mean of the members' points (7.)             0
+ *        pooled      (N,P,C)  fp32   mean of the members' features (7.)           0      (C > 0 only)
+ *   7. MEANS.  An fp64 sum of the members' fp32 values divided by the fp64 count and rounded once to fp32.  The sum's
+ *      shape depends on the member's position j within the voxel alone: groups of 16 consecutive members, each added one
+ *      after the other to +0.0; chunks of 64 consecutive groups, each combined by the aligned pairwise tree (groups 2k
+ *      and 2k+1, then pairs of pairs, ...; a missing group counts +0.0); the chunks added one after the other to +0.0.
+ *      Features are averaged and not renormalised (Open3D does the same for normals).
+ *   Every output is fully written.  No atomics on floating-point data, nothing synchronises, nothing is read back: two
+ *   calls are byte-equal, and the call can be captured into a HIP graph.
+ *   workspace: pointops_voxel_workspace_bytes(N, P, C); a short or null one is POINTOPS_EWORKSPACE with nothing written.
+ *   0 <= N < 65536 (a bigger batch goes in slices), 0 <= P <= 2^24, 0 <= C <= 1024 (C > 0 needs features and pooled),
+ *   voxel_size finite and > 0: anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing; P == 0
+ *   writes num_voxels = 0 and status = 0 only.
+ */
+size_t pointops_voxel_workspace_bytes(int64_t N, int64_t P, int64_t C);
+int pointops_voxel_downsample(const float* points, const int64_t* lengths, const float* features, const float* origin,
+                              int origin_per_cloud, int64_t N, int64_t P, int64_t C, float voxel_size,
+                              int64_t* num_voxels, int32_t* status, int64_t* inverse, int64_t* counts,
+                              int64_t* first_index, int64_t* coords, float* centroids, float* pooled, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

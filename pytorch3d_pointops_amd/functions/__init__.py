@@ -14,5 +14,6 @@ from .points_normals import estimate_pointcloud_local_coord_frames, estimate_poi
 from .ransac import RansacSolution, ransac_alignment
 from .sample_farthest_points import sample_farthest_points
 from .utils import convert_pointclouds_to_tensor, get_point_covariances, masked_gather, wmean
+from .voxel import VoxelDownsample, voxel_downsample, voxels_to_padded
 
 __all__ = [k for k in globals().keys() if not k.startswith("_")]

@@ -240,6 +240,18 @@ class Pointclouds:
 
         return segment_plane(self, **kwargs)
 
+    def voxel_downsample(self, voxel_size: float, **kwargs) -> "Pointclouds":
+        """A new batch with one point per occupied voxel of every cloud -- the centroid of the voxel's points -- and
+        every feature averaged over the same points (functions.voxel_downsample, same keywords, plus `check` of
+        functions.voxels_to_padded: raise when a cloud was refused; a refused cloud is empty otherwise)."""
+        from ..functions.voxel import voxel_downsample, voxels_to_padded
+
+        check = kwargs.pop("check", False)
+        r = voxels_to_padded(voxel_downsample(self, voxel_size=voxel_size, **kwargs), check=check)
+        num = r.num_voxels.tolist()
+        feats = {k: [t[n, :v] for n, v in enumerate(num)] for k, t in (r.features or {}).items()}
+        return Pointclouds([r.points[n, :v] for n, v in enumerate(num)], feats or None)
+
     # ------------------------------------------------------------------ single clouds, copies of clouds
     def get_cloud(self, index: int):
         """(points (P, 3), {name: (P, C)}) of one cloud (reference :938)."""
