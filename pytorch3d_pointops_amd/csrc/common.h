@@ -30,6 +30,14 @@ inline int check_launch(const char* what) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the rows of cloud n that count: P without `lengths`, else lengths[n] clamped to [0, P] (T: the caller's index width)
+template <class T = int>
+__device__ __forceinline__ T clamped_length(const int64_t* __restrict__ lengths, int n, int P) {
+  if (lengths == nullptr) return P;
+  const int64_t l = lengths[n];
+  return (T)(l < 0 ? 0 : (l > P ? P : l));
+}
+
 // Lays a workspace out as consecutive 256-byte aligned arrays.  With a null base it only sizes (take() returns null):
 // one layout function serves both an operator's *_workspace_bytes query and its entry.
 struct Carver {

@@ -49,12 +49,6 @@ __device__ __forceinline__ void cross3f(const float (&a)[3], const float (&b)[3]
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__device__ __forceinline__ int fpfh_length(const int64_t* __restrict__ lengths, int n, int P) {
-  if (lengths == nullptr) return P;
-  const int64_t len = lengths[n];
-  return (int)(len < 0 ? 0 : (len > P ? P : len));
-}
-
 template <int G>
 __global__ __launch_bounds__(kSpfhBlock) void spfh_kernel(const float* __restrict__ points,
                                                           const float* __restrict__ normals,
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(kSpfhBlock) void spfh_kernel(const float* __restric
   const int n = blockIdx.y;
   const int i0 = blockIdx.x * PTS;
   const int rows = min(PTS, P - i0);
-  const int len = fpfh_length(lengths, n, P);
+  const int len = clamped_length(lengths, n, P);
   for (int e = threadIdx.x; e < PTS * kFpfhBins; e += kSpfhBlock) s_cnt[e] = 0u;
   __syncthreads();
 
@@ -155,7 +149,7 @@ __global__ __launch_bounds__(kFpfhBlock) void fpfh_kernel(const float* __restric
   const int n = blockIdx.y;
   const int i0 = blockIdx.x * kFpfhPts;
   const int rows = min(kFpfhPts, P - i0);
-  const int len = fpfh_length(lengths, n, P);
+  const int len = clamped_length(lengths, n, P);
   const float* __restrict__ pts = points + (int64_t)n * P * 3;
   const int64_t* __restrict__ idx0 = idx + ((int64_t)n * P + i0) * K;
   for (int e = threadIdx.x; e < rows * K; e += kFpfhBlock) {

@@ -4,9 +4,8 @@
 //
 // The torch composition it replaces builds an (N, H, P) residual tensor.  Here nothing of that size exists:
 //
-//   1. plane_valid_count_kernel / plane_records_kernel   a workgroup per tile of 2048 rows (8 consecutive rows per
-//      thread) counts its valid rows; the second pass adds the counts of the tiles before its own and writes its valid
-//      rows, in ascending order (block_exclusive_sum), as 16-byte records (x, y, z, row), and the last tile M_n.
+//   1. compaction (consensus.h over PlaneRows)   the valid rows of a cloud, in ascending order, as 16-byte records
+//      (x, y, z, row), and their number M_n.
 //   2. plane_hypotheses_kernel   one lane per (cloud, hypothesis): draws three distinct records (or reads the caller's
 //      rows) and forms the plane in fp64 with its validity tests (plane_hypothesis.h).
 //   3. plane_score_kernel        the hot path, H M residuals per cloud.  One lane = HPL hypotheses with (a, b, c, d) in
@@ -16,102 +15,58 @@
 //      and every lane reads at the same address.  blockIdx.y splits the records of a cloud into chunks of kPlaneChunk;
 //      each (chunk, hypothesis) writes one int32.  POINTOPS_DEBUG="plane_lds=0|1" picks the path, "plane_hpl=1|2" the
 //      hypotheses per lane (default 2 above 256 hypotheses): the A/B of DESIGN 4.10.
-//   4. plane_count_kernel / plane_select_kernel   the 64-bit key selection of ransac.hip (ransac_select.h): integers only.
+//   4. selection (consensus.h)    the largest count at the lowest index; plane_select_kernel copies the winning plane
+//      into the candidate.
 //   5. plane_evaluate_kernel / plane_finish_kernel   mask, count, fp64 block partials of sum r^2 and of the moments of
-//      the inliers about a pivot; one finishing block per cloud applies the accept rule, writes the public outputs and
-//      solves the next candidate from the moments (ph_refit: covariance, sym3_eigen_f64, sign rule).
+//      the inliers about a pivot; one finishing block per cloud applies the accept rule (consensus.h), writes the
+//      public outputs and solves the next candidate from the moments (ph_refit: covariance, sym3_eigen_f64, sign rule).
 //
 // No atomics, no host read-back: bit-reproducible and capturable into a HIP graph.
 #include "common.h"
+#include "consensus.h"
 #include "debug.h"
 #include "plane_hypothesis.h"
-#include "ransac_select.h"
-#include "wave.h"
 
 namespace pointops {
 
 constexpr int kPlaneChunk = 512;  // records per scoring block (exported: pointops_plane_chunk)
-constexpr int kPlRows = 8;        // consecutive rows per thread of the compaction
-constexpr int kPlTile = kRsBlock * kPlRows;  // rows per step of the compaction (2048)
-constexpr int kPlRowsPerThread = 8;
-constexpr int kPlMaxBlocks = 32;  // evaluation partials per cloud
 constexpr int kPlPart = kPlaneMoments;  // doubles per evaluation partial: sum r^2, S q (3), S q q^T (6)
-
-inline int64_t pl_tiles(int64_t P) { return P > 0 ? ceil_div(P, (int64_t)kPlTile) : 1; }
-
-inline int pl_eval_blocks(int64_t P) {
-  const int64_t nb = ceil_div(P, (int64_t)kRsBlock * kPlRowsPerThread);
-  return (int)(nb < 1 ? 1 : (nb > kPlMaxBlocks ? kPlMaxBlocks : nb));
-}
 
 __device__ __forceinline__ bool pl_row_valid(const uint8_t* __restrict__ mask, int n, int P, int64_t i, int len) {
   return i >= 0 && i < len && (mask == nullptr || mask[(int64_t)n * P + i] != 0);
 }
 
 // ---------------------------------------------------------------------------------------------------- 1. compaction
-// Workgroup (tile, n) owns rows [tile * kPlTile, +kPlTile) of cloud n; a thread owns kPlRows consecutive rows of them,
-// so thread order is row order.  Bit k of the result: the thread's row k is valid.
-__device__ __forceinline__ int pl_tile_rows(const uint8_t* __restrict__ mask, int n, int P, int len, int& mine) {
-  const int first = blockIdx.x * kPlTile + (int)threadIdx.x * kPlRows;
-  int bits = 0;
-  mine = 0;
-#pragma unroll
-  for (int k = 0; k < kPlRows; ++k) {
-    const bool v = pl_row_valid(mask, n, P, first + k, len);
-    bits |= v ? (1 << k) : 0;
-    mine += v ? 1 : 0;
+// The row source of the compaction: a valid row's key is 0.
+struct PlaneRows {
+  using Record = float4;
+  const float* points;
+  const int64_t* lengths;
+  const uint8_t* mask;
+  int P, len;
+  __device__ __forceinline__ void enter(int n) { len = clamped_length(lengths, n, P); }
+  __device__ __forceinline__ int key(int n, int i) const { return pl_row_valid(mask, n, P, i, len) ? 0 : -1; }
+  __device__ __forceinline__ void store(float4* __restrict__ out, int at, int n, int i, int) const {
+    const float* __restrict__ p = points + (int64_t)n * P * 3 + (int64_t)i * 3;
+    out[at] = make_float4(p[0], p[1], p[2], __int_as_float(i));
   }
-  return bits;
-}
-
-__global__ __launch_bounds__(kRsBlock) void plane_valid_count_kernel(
-    const int64_t* __restrict__ lengths, const uint8_t* __restrict__ mask, int P, int* __restrict__ tile_valid) {
-  __shared__ int s_wsum[kRsWaves];
-  const int n = blockIdx.y;
-  int mine, total;
-  pl_tile_rows(mask, n, P, rs_length(lengths, n, P), mine);
-  block_exclusive_sum<kRsWaves>(mine, s_wsum, total);
-  if (threadIdx.x == 0) tile_valid[(int64_t)n * gridDim.x + blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kRsBlock) void plane_records_kernel(
-    const float* __restrict__ points, const int64_t* __restrict__ lengths, const uint8_t* __restrict__ mask, int P,
-    const int* __restrict__ tile_valid, float4* __restrict__ records, int* __restrict__ num_valid) {
-  __shared__ int s_wsum[kRsWaves];
-  const int n = blockIdx.y, tile = blockIdx.x, tiles = gridDim.x;
-  const float* __restrict__ ps = points + (int64_t)n * P * 3;
-  float4* __restrict__ out = records + (int64_t)n * P;
-  int base = 0;
-  for (int t = 0; t < tile; ++t) base += tile_valid[(int64_t)n * tiles + t];  // (uniform: scalar loads)
-  int mine, total;
-  const int bits = pl_tile_rows(mask, n, P, rs_length(lengths, n, P), mine);
-  int at = base + block_exclusive_sum<kRsWaves>(mine, s_wsum, total);
-  const int first = tile * kPlTile + (int)threadIdx.x * kPlRows;
-#pragma unroll
-  for (int k = 0; k < kPlRows; ++k) {
-    if (!(bits & (1 << k))) continue;
-    const int64_t i = first + k;
-    out[at] = make_float4(ps[i * 3], ps[i * 3 + 1], ps[i * 3 + 2], __int_as_float((int)i));
-    ++at;
-  }
-  if (tile == tiles - 1 && threadIdx.x == 0) num_valid[n] = base + total;
-}
+};
 
 // ---------------------------------------------------------------------------------------------------- 2. hypotheses
-__global__ __launch_bounds__(kRsBlock) void plane_hypotheses_kernel(
+__global__ __launch_bounds__(kCsBlock) void plane_hypotheses_kernel(
     const float* __restrict__ points, const int64_t* __restrict__ lengths, const uint8_t* __restrict__ mask,
     const int64_t* __restrict__ samples_in, int P, int H, int64_t seed, int64_t first_cloud, PlaneCone cone,
     const float4* __restrict__ records, const int* __restrict__ num_valid, float4* __restrict__ ws_plane,
     int* __restrict__ ws_valid, float* __restrict__ hyp_planes, int64_t* __restrict__ samples_out) {
   const int n = blockIdx.y;
-  const int h = blockIdx.x * kRsBlock + (int)threadIdx.x;
+  const int h = blockIdx.x * kCsBlock + (int)threadIdx.x;
   if (h >= H) return;
   const int64_t slot = (int64_t)n * H + h;
   float p[3][3];
   int64_t rows[3] = {-1, -1, -1};
   bool valid;
   if (samples_in != nullptr) {
-    const int len = rs_length(lengths, n, P);
+    const int len = clamped_length(lengths, n, P);
     valid = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -155,7 +110,7 @@ __global__ __launch_bounds__(kRsBlock) void plane_hypotheses_kernel(
 // into an LDS tile and every lane reads the same address (a broadcast).  HPL hypotheses per lane: lane t of tile b owns hypotheses
 // (b HPL + k) 256 + t, so every record fetched feeds HPL residuals per lane.  The results are the same in every form.
 template <bool LDS, int HPL>
-__global__ __launch_bounds__(kRsBlock) void plane_score_kernel(
+__global__ __launch_bounds__(kCsBlock) void plane_score_kernel(
     const float4* __restrict__ records, const int* __restrict__ num_valid, const float4* __restrict__ ws_plane,
     const int* __restrict__ ws_valid, int P, int H, int S, float thr, int* __restrict__ partials) {
   __shared__ float4 s_rec[LDS ? kPlaneChunk : 1];
@@ -166,14 +121,14 @@ __global__ __launch_bounds__(kRsBlock) void plane_score_kernel(
   const int end = min(beg + kPlaneChunk, M);
   const float4* __restrict__ rec = records + (int64_t)n * P;
   if constexpr (LDS) {
-    for (int t = threadIdx.x; t < end - beg; t += kRsBlock) s_rec[t] = rec[beg + t];
+    for (int t = threadIdx.x; t < end - beg; t += kCsBlock) s_rec[t] = rec[beg + t];
     __syncthreads();
   }
   int h[HPL];
   bool valid[HPL], any = false;
 #pragma unroll
   for (int k = 0; k < HPL; ++k) {
-    h[k] = (blockIdx.x * HPL + k) * kRsBlock + (int)threadIdx.x;
+    h[k] = (blockIdx.x * HPL + k) * kCsBlock + (int)threadIdx.x;
     valid[k] = h[k] < H && ws_valid[(int64_t)n * H + h[k]] != 0;
     any = any || valid[k];
   }
@@ -214,43 +169,12 @@ __global__ __launch_bounds__(kRsBlock) void plane_score_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------- 4. selection
-// As ransac_count_kernel: one lane per (cloud, hypothesis) sums its chunk partials, writes the optional `counts` and
-// reduces the tile's largest key -- count in the high word, the inverted index in the low one; 0 = no valid hypothesis.
-__global__ __launch_bounds__(kRsBlock) void plane_count_kernel(
-    const int* __restrict__ num_valid, const int* __restrict__ partials, const int* __restrict__ ws_valid, int H, int S,
-    int* __restrict__ counts, unsigned long long* __restrict__ tile_keys) {
-  __shared__ unsigned long long s_key[kRsWaves];
-  const int n = blockIdx.y;
-  const int live = (num_valid[n] + kPlaneChunk - 1) / kPlaneChunk;  // <= S
-  const int h = blockIdx.x * kRsBlock + (int)threadIdx.x;
-  unsigned long long key = 0ull;
-  if (h < H) {
-    int c = -1;
-    if (ws_valid[(int64_t)n * H + h] != 0) {
-      c = 0;
-#pragma unroll 8
-      for (int k = 0; k < live; ++k) c += partials[((int64_t)n * S + k) * H + h];
-      key = ((unsigned long long)(uint32_t)c << 32) | (uint32_t)(0xffffffffu - (uint32_t)h);
-    }
-    if (counts != nullptr) counts[(int64_t)n * H + h] = c;
-  }
-  key = rs_block_max(key, s_key);
-  if (threadIdx.x == 0) tile_keys[(int64_t)n * gridDim.x + blockIdx.x] = key;
-}
-
-__global__ __launch_bounds__(kRsBlock) void plane_select_kernel(
+__global__ __launch_bounds__(kCsBlock) void plane_select_kernel(
     const unsigned long long* __restrict__ tile_keys, int tiles, const float4* __restrict__ ws_plane, int H,
     int64_t* __restrict__ best, float4* __restrict__ cand_plane, int* __restrict__ cand_ok) {
-  __shared__ unsigned long long s_key[kRsWaves];
   const int n = blockIdx.x;
-  unsigned long long key = 0ull;
-  for (int t = threadIdx.x; t < tiles; t += kRsBlock) {
-    const unsigned long long o = tile_keys[(int64_t)n * tiles + t];
-    key = o > key ? o : key;
-  }
-  key = rs_block_max(key, s_key);
+  const int64_t b = cs_best(tile_keys, tiles, n);
   if (threadIdx.x != 0) return;
-  const int64_t b = key == 0ull ? -1 : (int64_t)(0xffffffffu - (uint32_t)(key & 0xffffffffull));
   best[n] = b;
   cand_ok[n] = b < 0 ? 0 : 1;
   cand_plane[n] = b < 0 ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : ws_plane[(int64_t)n * H + b];
@@ -260,16 +184,14 @@ __global__ __launch_bounds__(kRsBlock) void plane_select_kernel(
 // Mask (one byte per row), count, sum of r^2 and -- MOMENTS: a refit follows -- the moments about the pivot over the
 // inliers of the candidate plane of every cloud.  The pivot is the cloud's first valid row (record 0).
 template <bool MOMENTS>
-__global__ __launch_bounds__(kRsBlock) void plane_evaluate_kernel(
+__global__ __launch_bounds__(kCsBlock) void plane_evaluate_kernel(
     const float* __restrict__ points, const int64_t* __restrict__ lengths, const uint8_t* __restrict__ mask,
     const float4* __restrict__ cand_plane, const int* __restrict__ cand_ok, const float4* __restrict__ records,
     const int* __restrict__ num_valid, const int* __restrict__ stopped, int first, int P, float thr,
     uint8_t* __restrict__ cand_mask, double* __restrict__ part, int* __restrict__ part_count) {
   constexpr int kSums = MOMENTS ? kPlPart : 1;
-  __shared__ double s_sum[kRsWaves][kSums];
-  __shared__ int s_cnt[kRsWaves];
   const int n = blockIdx.y, nb = gridDim.x;
-  const int len = rs_length(lengths, n, P);
+  const int len = clamped_length(lengths, n, P);
   // a cloud that has stopped keeps the mask it accepted: its candidate is not evaluated and nothing is written over
   const bool skip = !first && stopped[n] != 0;
   const bool none = skip || cand_ok[n] == 0 || num_valid[n] == 0;
@@ -281,7 +203,7 @@ __global__ __launch_bounds__(kRsBlock) void plane_evaluate_kernel(
 #pragma unroll
   for (int m = 0; m < kSums; ++m) sum[m] = 0.0;
   int cnt = 0;
-  for (int i = blockIdx.x * kRsBlock + (int)threadIdx.x; i < P; i += nb * kRsBlock) {
+  for (int i = blockIdx.x * kCsBlock + (int)threadIdx.x; i < P; i += nb * kCsBlock) {
     bool in = false;
     if (!none && pl_row_valid(mask, n, P, i, len)) {
       const float x = ps[(int64_t)i * 3], y = ps[(int64_t)i * 3 + 1], z = ps[(int64_t)i * 3 + 2];
@@ -307,61 +229,33 @@ __global__ __launch_bounds__(kRsBlock) void plane_evaluate_kernel(
     cnt += in ? 1 : 0;
     if (!skip) cand_mask[(int64_t)n * P + i] = in ? 1 : 0;
   }
-#pragma unroll
-  for (int m = 0; m < kSums; ++m) sum[m] = wave_sum(sum[m]);
-  cnt = wave_sum(cnt);
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-#pragma unroll
-    for (int m = 0; m < kSums; ++m) s_sum[threadIdx.x / kWave][m] = sum[m];
-    s_cnt[threadIdx.x / kWave] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kRsWaves; ++w) {
-#pragma unroll
-      for (int m = 0; m < kSums; ++m) sum[m] += s_sum[w][m];
-      cnt += s_cnt[w];
-    }
-    double* __restrict__ o = part + ((int64_t)n * nb + blockIdx.x) * kPlPart;
-#pragma unroll
-    for (int m = 0; m < kSums; ++m) o[m] = sum[m];
-    part_count[(int64_t)n * nb + blockIdx.x] = cnt;
-  }
+  const int64_t slot = (int64_t)n * nb + blockIdx.x;
+  cs_block_partials(sum, cnt, nb, part + (int64_t)n * kPlPart * nb + blockIdx.x, part_count + slot);
 }
 
-// One block per cloud: the candidate's count and rmse from the block partials (ascending), the accept rule, and -- on
-// acceptance -- the public plane, count and rmse and the buffer that holds the accepted mask; with `more` (another
-// refit follows) thread 0 then solves the next candidate from the moments of the mask it has just accepted.  `first`: the winner's own evaluation, always
-// accepted.  stopped[n] != 0: a refit was rejected (or no hypothesis is valid) and the cloud keeps what it has.
-__global__ __launch_bounds__(kRsBlock) void plane_finish_kernel(
+// One block per cloud: the accept rule and -- on acceptance -- the public plane, count and rmse and the buffer that
+// holds the accepted mask; with `more` (another refit follows) thread 0 then solves the next candidate from the moments
+// of the mask it has just accepted.
+__global__ __launch_bounds__(kCsBlock) void plane_finish_kernel(
     const double* __restrict__ part, const int* __restrict__ part_count, int nb, int first, int more,
     const int64_t* __restrict__ best, float4* __restrict__ cand_plane, int* __restrict__ cand_ok,
     int buffer, const float4* __restrict__ records, const int* __restrict__ num_valid, int P, PlaneCone cone,
     int* __restrict__ stopped, int* __restrict__ which, float* __restrict__ planes, int64_t* __restrict__ num_inliers,
     float* __restrict__ rmse) {
-  __shared__ double s_part[kPlMaxBlocks * kPlPart];  // (one load per thread instead of nb dependent rounds in thread 0)
+  __shared__ double s_part[kCsMaxBlocks * kPlPart];  // (one load per thread instead of nb dependent rounds in thread 0)
   const int n = blockIdx.x;
-  for (int t = threadIdx.x; t < nb * kPlPart; t += kRsBlock) {
-    const bool written = more || t % kPlPart == 0;  // (without a refit to follow only the sums of r^2 exist)
-    s_part[t] = written ? part[(int64_t)n * nb * kPlPart + t] : 0.0;
+  if (more) {
+    for (int t = threadIdx.x; t < nb * kPlPart; t += kCsBlock) s_part[t] = part[(int64_t)n * nb * kPlPart + t];
   }
-  int cnt = 0;
-  for (int b = 0; b < nb; ++b) cnt += part_count[(int64_t)n * nb + b];  // (every thread: the decision is uniform)
-  const bool accept = first ? true : (stopped[n] == 0 && cand_ok[n] != 0 && (int64_t)cnt >= num_inliers[n]);
-  __syncthreads();  // every thread has read stopped / cand_ok / num_inliers before thread 0 writes them; s_part is full
-  if (!accept) {
-    if (threadIdx.x == 0) stopped[n] = 1;
-    return;
-  }
+  int cnt;
+  double sum;  // (the barrier of cs_accept also completes s_part; cand_ok is read before thread 0 writes it)
+  const bool usable = cand_ok[n] != 0;
+  const double* __restrict__ sums = part + (int64_t)n * kPlPart * nb;  // (of r^2: row 0 of the cloud's partials)
+  if (!cs_accept(sums, part_count, nb, n, first, usable, stopped, num_inliers, cnt, sum)) return;
   if (threadIdx.x == 0) {
-    if (first) stopped[n] = best[n] < 0 ? 1 : 0;
+    cs_publish(n, first, best, cnt, sum, stopped, num_inliers, rmse);
     which[n] = buffer;
     const float4 pl = cand_plane[n];
-    double sum = 0.0;
-    for (int b = 0; b < nb; ++b) sum += s_part[b * kPlPart];
-    num_inliers[n] = cnt;
-    rmse[n] = (float)sqrt(sum / (double)(cnt > 1 ? cnt : 1));
     ((float4*)planes)[n] = pl;
     if (more) {
       double mom[kPlaneMoments];
@@ -370,7 +264,7 @@ __global__ __launch_bounds__(kRsBlock) void plane_finish_kernel(
       for (int m = 1; m < kPlaneMoments; ++m) mom[m] = 0.0;
       for (int b = 0; b < nb; ++b) {
 #pragma unroll
-        for (int m = 1; m < kPlaneMoments; ++m) mom[m] += s_part[b * kPlPart + m];
+        for (int m = 1; m < kPlaneMoments; ++m) mom[m] += s_part[m * nb + b];
       }
       float next[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       bool ok = false;
@@ -386,12 +280,12 @@ __global__ __launch_bounds__(kRsBlock) void plane_finish_kernel(
 }
 
 // The public mask: the candidate mask of the evaluation each cloud accepted last (which[n] names its buffer).
-__global__ __launch_bounds__(kRsBlock) void plane_mask_kernel(
+__global__ __launch_bounds__(kCsBlock) void plane_mask_kernel(
     const uint8_t* __restrict__ cand_mask, const int* __restrict__ which, int64_t N, int P, uint8_t* __restrict__ mask) {
   const int n = blockIdx.y;
   const uint8_t* __restrict__ src = cand_mask + ((int64_t)which[n] * N + n) * P;
   uint8_t* __restrict__ dst = mask + (int64_t)n * P;
-  const int stride = gridDim.x * kRsBlock, at = blockIdx.x * kRsBlock + (int)threadIdx.x;
+  const int stride = gridDim.x * kCsBlock, at = blockIdx.x * kCsBlock + (int)threadIdx.x;
   if ((P & 15) == 0 && (((uintptr_t)mask | (uintptr_t)cand_mask) & 15) == 0) {  // sixteen rows per access
     for (int i = at; i < P / 16; i += stride) ((uint4*)dst)[i] = ((const uint4*)src)[i];
     return;
@@ -400,57 +294,40 @@ __global__ __launch_bounds__(kRsBlock) void plane_mask_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
-struct PlaneLayout {
+struct PlaneLayout : CsLayout {
   float4* records;      // (N, P)
-  int* num_valid;       // (N,)
-  int* tile_valid;      // (N, ceil(P / 2048))
   float4* hyp_plane;    // (N, H)
-  int* hyp_valid;       // (N, H)
-  int* partials;        // (N, S, H)
-  unsigned long long* tile_keys;  // (N, ceil(H / 256))
   float4* cand_plane;   // (N,)
   int* cand_ok;         // (N,)
   uint8_t* cand_mask;   // (2, N, P): the evaluations alternate, so an accepted mask outlives the next candidate
   int* which;           // (N,) the buffer of the accepted mask
-  double* part;         // (N, nb, kPlPart)
-  int* part_count;      // (N, nb)
-  int* stopped;         // (N,)
+  double* part;         // (N, kPlPart, nb)
   size_t bytes;
 };
 
 static PlaneLayout plane_layout(void* ws, int64_t N, int64_t P, int64_t H) {
   Carver c(ws);
   PlaneLayout l;
+  static_cast<CsLayout&>(l) = cs_layout(c, N, P, H, kPlaneChunk);
   const size_t n = (size_t)N, p = (size_t)P, h = (size_t)H;
-  const size_t S = (size_t)ceil_div(P, kPlaneChunk), nb = (size_t)pl_eval_blocks(P);
   l.records = (float4*)c.take(sizeof(float4) * n * p);
-  l.num_valid = (int*)c.take(sizeof(int) * n);
-  l.tile_valid = (int*)c.take(sizeof(int) * n * (size_t)pl_tiles(P));
   l.hyp_plane = (float4*)c.take(sizeof(float4) * n * h);
-  l.hyp_valid = (int*)c.take(sizeof(int) * n * h);
-  l.partials = (int*)c.take(sizeof(int) * n * S * h);
-  l.tile_keys = (unsigned long long*)c.take(sizeof(unsigned long long) * n * (size_t)ceil_div(H, kRsBlock));
   l.cand_plane = (float4*)c.take(sizeof(float4) * n);
   l.cand_ok = (int*)c.take(sizeof(int) * n);
   l.cand_mask = (uint8_t*)c.take(2 * n * p);
   l.which = (int*)c.take(sizeof(int) * n);
-  l.part = (double*)c.take(sizeof(double) * n * nb * kPlPart);
-  l.part_count = (int*)c.take(sizeof(int) * n * nb);
-  l.stopped = (int*)c.take(sizeof(int) * n);
+  l.part = (double*)c.take(sizeof(double) * n * (size_t)cs_eval_blocks(P) * kPlPart);
   l.bytes = c.off;
   return l;
 }
 
-static bool plane_shape_ok(int64_t N, int64_t P, int64_t H) {
-  // (the chunks of a cloud are a grid's y coordinate, the tiles of hypotheses its x, the cloud its z)
-  return N >= 0 && N < 65536 && P >= 0 && P <= 65535LL * kPlaneChunk && H >= 1 && H <= (1LL << 24);
-}
+static bool plane_shape_ok(int64_t N, int64_t P, int64_t H) { return cs_shape_ok(N, P, H, kPlaneChunk); }
 
 template <bool LDS, int HPL>
 static void plane_launch_score(const PlaneLayout& l, int64_t N, int64_t P, int64_t H, unsigned S, float thr,
                                hipStream_t stream) {
-  const unsigned tiles = (unsigned)ceil_div(H, (int64_t)kRsBlock * HPL);
-  hipLaunchKernelGGL((plane_score_kernel<LDS, HPL>), dim3(tiles, S, (unsigned)N), dim3(kRsBlock), 0, stream,
+  const unsigned tiles = (unsigned)ceil_div(H, (int64_t)kCsBlock * HPL);
+  hipLaunchKernelGGL((plane_score_kernel<LDS, HPL>), dim3(tiles, S, (unsigned)N), dim3(kCsBlock), 0, stream,
                      (const float4*)l.records, (const int*)l.num_valid, (const float4*)l.hyp_plane,
                      (const int*)l.hyp_valid, (int)P, (int)H, (int)S, thr, l.partials);
 }
@@ -495,48 +372,43 @@ extern "C" int pointops_segment_plane(
   cone.a[1] = use_axis ? axis_y : 0.0f;
   cone.a[2] = use_axis ? axis_z : 0.0f;
   cone.cos_max = use_axis ? cos_max_angle : 0.0f;
-  const unsigned tiles = (unsigned)ceil_div(H, kRsBlock), S = (unsigned)ceil_div(P, kPlaneChunk);
-  const int nb = pl_eval_blocks(P);
+  const CsGrid g(N, P, H, kPlaneChunk);
+  const dim3 block(kCsBlock);
+  const unsigned S = g.S;
 
-  const dim3 tile_grid((unsigned)pl_tiles(P), (unsigned)N);
-  hipLaunchKernelGGL(plane_valid_count_kernel, tile_grid, dim3(kRsBlock), 0, stream, lengths, mask, (int)P,
-                     l.tile_valid);
-  hipLaunchKernelGGL(plane_records_kernel, tile_grid, dim3(kRsBlock), 0, stream, points, lengths, mask, (int)P,
-                     (const int*)l.tile_valid, l.records, l.num_valid);
-  hipLaunchKernelGGL(plane_hypotheses_kernel, dim3(tiles, (unsigned)N), dim3(kRsBlock), 0, stream, points, lengths,
-                     mask, samples_in, (int)P, (int)H, seed, first_cloud, cone, (const float4*)l.records,
-                     (const int*)l.num_valid, l.hyp_plane, l.hyp_valid, hyp_planes, samples_out);
+  cs_launch_compact(PlaneRows{points, lengths, mask, (int)P, 0}, g, l, P, l.records, stream);
+  hipLaunchKernelGGL(plane_hypotheses_kernel, g.hyp, block, 0, stream, points, lengths, mask, samples_in, (int)P,
+                     (int)H, seed, first_cloud, cone, (const float4*)l.records, (const int*)l.num_valid, l.hyp_plane,
+                     l.hyp_valid, hyp_planes, samples_out);
   if (S > 0) {
     // (the defaults are the winners of the A/B of DESIGN 4.10; a tile of hypotheses is 256 HPL wide)
     const bool lds = debug_knob("plane_lds", 1) != 0;
-    const long hpl = debug_knob("plane_hpl", H > kRsBlock ? 2 : 1);
+    const long hpl = debug_knob("plane_hpl", H > kCsBlock ? 2 : 1);
     if (lds && hpl == 2) plane_launch_score<true, 2>(l, N, P, H, S, thr, stream);
     else if (lds) plane_launch_score<true, 1>(l, N, P, H, S, thr, stream);
     else if (hpl == 2) plane_launch_score<false, 2>(l, N, P, H, S, thr, stream);
     else plane_launch_score<false, 1>(l, N, P, H, S, thr, stream);
   }
-  hipLaunchKernelGGL(plane_count_kernel, dim3(tiles, (unsigned)N), dim3(kRsBlock), 0, stream, (const int*)l.num_valid,
-                     (const int*)l.partials, (const int*)l.hyp_valid, (int)H, (int)S, counts, l.tile_keys);
-  hipLaunchKernelGGL(plane_select_kernel, dim3((unsigned)N), dim3(kRsBlock), 0, stream,
-                     (const unsigned long long*)l.tile_keys, (int)tiles, (const float4*)l.hyp_plane, (int)H, best,
-                     l.cand_plane, l.cand_ok);
+  cs_launch_count<kPlaneChunk>(g, l, H, counts, stream);
+  hipLaunchKernelGGL(plane_select_kernel, g.cloud, block, 0, stream, (const unsigned long long*)l.tile_keys,
+                     (int)g.tiles, (const float4*)l.hyp_plane, (int)H, best, l.cand_plane, l.cand_ok);
   int rc = check_launch("segment_plane");
   const int refits = P == 0 ? 0 : refine_steps;  // (no row, nothing to refit)
   for (int step = 0; step <= refits && rc == POINTOPS_OK; ++step) {
     const int more = step < refits ? 1 : 0;
     auto* evaluate = more ? plane_evaluate_kernel<true> : plane_evaluate_kernel<false>;
-    hipLaunchKernelGGL(evaluate, dim3((unsigned)nb, (unsigned)N), dim3(kRsBlock), 0, stream, points, lengths, mask,
-                       (const float4*)l.cand_plane, (const int*)l.cand_ok, (const float4*)l.records,
-                       (const int*)l.num_valid, (const int*)l.stopped, step == 0 ? 1 : 0, (int)P, thr,
-                       l.cand_mask + (size_t)(step & 1) * (size_t)N * (size_t)P, l.part, l.part_count);
-    hipLaunchKernelGGL(plane_finish_kernel, dim3((unsigned)N), dim3(kRsBlock), 0, stream, (const double*)l.part,
-                       (const int*)l.part_count, nb, step == 0 ? 1 : 0, more, (const int64_t*)best, l.cand_plane,
+    hipLaunchKernelGGL(evaluate, g.eval, block, 0, stream, points, lengths, mask, (const float4*)l.cand_plane,
+                       (const int*)l.cand_ok, (const float4*)l.records, (const int*)l.num_valid, (const int*)l.stopped,
+                       step == 0 ? 1 : 0, (int)P, thr, l.cand_mask + (size_t)(step & 1) * (size_t)N * (size_t)P, l.part,
+                       l.part_count);
+    hipLaunchKernelGGL(plane_finish_kernel, g.cloud, block, 0, stream, (const double*)l.part,
+                       (const int*)l.part_count, g.nb, step == 0 ? 1 : 0, more, (const int64_t*)best, l.cand_plane,
                        l.cand_ok, step & 1, (const float4*)l.records, (const int*)l.num_valid, (int)P, cone, l.stopped,
                        l.which, planes, num_inliers, rmse);
     rc = check_launch("segment_plane");
   }
   if (rc == POINTOPS_OK && P > 0) {
-    hipLaunchKernelGGL(plane_mask_kernel, dim3((unsigned)nb, (unsigned)N), dim3(kRsBlock), 0, stream,
+    hipLaunchKernelGGL(plane_mask_kernel, g.eval, block, 0, stream,
                        (const uint8_t*)l.cand_mask, (const int*)l.which, N, (int)P, inlier_mask);
     rc = check_launch("segment_plane");
   }

@@ -1,12 +1,12 @@
 // plane_hypothesis.h -- the per-lane routines of plane.hip, __host__ __device__: the plane through three points with
-// its validity tests, the sign rule, the fp32 residual, and the refit of a plane from fp64 moments.  The counter-based
-// draws are those of ransac_hypothesis.h (rh_hash32 / rh_draw), included and not copied.
+// its validity tests, the sign rule, the fp32 residual, and the refit of a plane from fp64 moments.  (The counter-based
+// draws are those of consensus_draw.h.)
 //
 // They live here so that a host program can run them on millions of triples without a GPU
 // (tests/native/plane_hypothesis_main.cpp); the kernels include this header and nothing else defines the functions.
 // The normative text is the comment of pointops_segment_plane in include/pointops_amd.h.
 #pragma once
-#include "ransac_hypothesis.h"
+#include "small_solvers.h"
 
 namespace pointops {
 

@@ -76,12 +76,6 @@ __device__ __forceinline__ void pa_block_sum(const double (&acc)[M], double (*s_
   }
 }
 
-__device__ __forceinline__ int64_t pa_length(const int64_t* __restrict__ lengths, int n, int P) {
-  if (lengths == nullptr) return P;
-  const int64_t l = lengths[n];
-  return l < 0 ? 0 : (l > P ? P : l);
-}
-
 // The pivots of cloud n: row 0 of X and of Y (zero for a cloud without rows).
 template <int D>
 __device__ __forceinline__ void pa_pivots(const float* __restrict__ X, const float* __restrict__ Y, int n, int P, int P2,
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(kPaBlock) void alignment_moments_kernel(
   constexpr int M = S::kCount;
   __shared__ double s_part[kPaWaves][M];
   const int n = blockIdx.y, nb = gridDim.x;
-  const int64_t len = pa_length(lengths, n, P);
+  const int64_t len = clamped_length<int64_t>(lengths, n, P);
   double px[D], py[D];
   pa_pivots<D>(X, Y, n, P, P2, len, px, py);
   const float* __restrict__ xs = X + (int64_t)n * P * D;
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(kWave) void alignment_solve_kernel(
   __syncthreads();
   if (threadIdx.x != 0) return;
   double px[D], py[D], Rd[D][D], Td[D], sd, sg[D];
-  pa_pivots<D>(X, Y, n, P, P2, pa_length(lengths, n, P), px, py);
+  pa_pivots<D>(X, Y, n, P, P2, clamped_length<int64_t>(lengths, n, P), px, py);
   pa_solve<D>(s_mom, px, py, estimate_scale != 0, allow_reflection != 0, eps, Rd, Td, sd, sg);
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -185,7 +179,7 @@ __global__ __launch_bounds__(kPaBlock) void icp_apply_kernel(
     const float* __restrict__ s, int P, int P2, float* __restrict__ Xt, double* __restrict__ partials) {
   __shared__ double s_part[kPaWaves][1];
   const int n = blockIdx.y, nb = gridDim.x;
-  const int64_t len = pa_length(lengths, n, P);
+  const int64_t len = clamped_length<int64_t>(lengths, n, P);
   float r[D][D], t[D];
 #pragma unroll
   for (int a = 0; a < D; ++a) {
@@ -234,7 +228,7 @@ __global__ __launch_bounds__(kPaBlock) void icp_finish_kernel(const double* __re
   for (int n = threadIdx.x; n < N; n += kPaBlock) {
     double v = 0.0;
     for (int b = 0; b < nb; ++b) v += partials[(int64_t)n * nb + b];
-    const double len = (double)pa_length(lengths, n, P);
+    const double len = (double)clamped_length<int64_t>(lengths, n, P);
     const float cur = (float)sqrt(v / (len > 1e-9 ? len : 1e-9));
     const float prev = rmse[n];
     const float rel = first ? 1.0f : (prev > 0.0f ? (prev - cur) / prev : 0.0f);
@@ -256,7 +250,7 @@ __global__ __launch_bounds__(kPaBlock) void alignment_backward_kernel(
   if (row >= rows) return;
   const int n = (int)(row / P);
   const int64_t i = row - (int64_t)n * P;
-  const int64_t len = pa_length(lengths, n, P);
+  const int64_t len = clamped_length<int64_t>(lengths, n, P);
   if (i >= len) {
 #pragma unroll
     for (int d = 0; d < D; ++d) {

@@ -5,10 +5,8 @@
 // The torch composition it replaces solves an (N H)-batched SVD and builds an (N, H, C) residual tensor (hundreds of MB
 // at H = 4096, C = 65536).  Here nothing of that size exists:
 //
-//   1. ransac_pair_count_kernel / ransac_pairs_kernel   a workgroup per tile of 2048 rows (8 consecutive rows per
-//      thread) counts its valid pairs; the second pass adds the counts of the tiles before its own and writes its valid
-//      pairs, in ascending row order (block_exclusive_sum), as 32-byte records (x, y, row, pad), and the last tile M_n.
-//      (One workgroup per cloud walking all the tiles was bound by one CU's gather latency: DESIGN 4.8.)
+//   1. compaction (consensus.h over RansacPairs)   the valid pairs of a cloud, in ascending row order, as 32-byte
+//      records (x, y, row, pad), and their number M_n.
 //   2. ransac_hypotheses_kernel   one lane per (cloud, hypothesis): draws three distinct records (or reads the caller's
 //      rows), runs the validity tests and solves the three-pair alignment in fp64 (ransac_hypothesis.h).
 //   3. ransac_score_kernel        the hot path, H M residuals per cloud.  One lane = one hypothesis with A = s R and T
@@ -16,28 +14,22 @@
 //      blockIdx and the loop counter only, so the records arrive through the scalar path (s_load_dwordx8 into SGPRs,
 //      as knn.hip streams p2) and feed the VALU as scalar operands.  blockIdx.y splits the records of a cloud into
 //      chunks of kRansacChunk so that a small N H still fills the device; each (chunk, hypothesis) writes one int32.
-//   4. ransac_count_kernel        one lane per hypothesis sums its chunk partials and a tile of 256 reduces the 64-bit
-//      key (count high, inverted index low); ransac_select_kernel, one workgroup per cloud, reduces the tile keys to
-//      the winner and writes best and the candidate transform: integers only.  (One workgroup per cloud summing all
-//      S H partials itself took as long as the scoring at H = 4096, M = 65536: 256 chunks of 4096 counts on 8 CUs.)
+//   4. selection (consensus.h)    the largest count at the lowest index; ransac_select_kernel copies the winner's
+//      transform into the candidate.
 //   5. ransac_evaluate_kernel / ransac_finish_kernel   mask, count and fp64 block partials of sum d2 of a candidate
-//      transform; one finishing block per cloud applies the accept rule and writes the public outputs.  Between two
-//      evaluations the refinement is pointops_points_alignment weighted by the current mask, on the same stream.
+//      transform; one finishing block per cloud applies the accept rule (consensus.h) and writes the public outputs.
+//      Between two evaluations the refinement is pointops_points_alignment weighted by the current mask, on the same
+//      stream.
 //
 // No atomics, no host read-back: bit-reproducible and capturable into a HIP graph.
 #include "common.h"
+#include "consensus.h"
 #include "debug.h"
 #include "ransac_hypothesis.h"
-#include "ransac_select.h"
-#include "wave.h"
 
 namespace pointops {
 
 constexpr int kRansacChunk = 256;  // records per scoring block (exported: pointops_ransac_chunk)
-constexpr int kRsPairRows = 8;     // consecutive rows per thread of the compaction
-constexpr int kRsPairTile = kRsBlock * kRsPairRows;  // rows per step of the compaction (2048)
-constexpr int kRsRowsPerThread = 8;
-constexpr int kRsMaxBlocks = 32;   // evaluation partials per cloud
 
 struct alignas(32) RansacRecord {
   float x[3];
@@ -47,13 +39,6 @@ struct alignas(32) RansacRecord {
 };
 static_assert(sizeof(RansacRecord) == 32, "a record is two 16-byte stores");
 
-inline int64_t rs_pair_tiles(int64_t P) { return P > 0 ? ceil_div(P, (int64_t)kRsPairTile) : 1; }
-
-inline int rs_eval_blocks(int64_t P) {
-  const int64_t nb = ceil_div(P, (int64_t)kRsBlock * kRsRowsPerThread);
-  return (int)(nb < 1 ? 1 : (nb > kRsMaxBlocks ? kRsMaxBlocks : nb));
-}
-
 // the row of Y that row i of X is matched to, or -1 when the row is no valid correspondence
 __device__ __forceinline__ int rs_target(const int64_t* __restrict__ corr, int n, int P1, int i, int len1, int len2) {
   if (i < 0 || i >= len1) return -1;
@@ -62,61 +47,28 @@ __device__ __forceinline__ int rs_target(const int64_t* __restrict__ corr, int n
 }
 
 // ---------------------------------------------------------------------------------------------------- 1. compaction
-// Workgroup (tile, n) owns rows [tile * kRsPairTile, +kRsPairTile) of cloud n; a thread owns kRsPairRows consecutive
-// rows of them, so thread order is row order.  The targets of the thread's rows; returns how many are valid.
-__device__ __forceinline__ int rs_tile_targets(const int64_t* __restrict__ corr, int n, int P1, int len1, int len2,
-                                               int (&j)[kRsPairRows]) {
-  const int first = blockIdx.x * kRsPairTile + (int)threadIdx.x * kRsPairRows;
-  int mine = 0;
-#pragma unroll
-  for (int k = 0; k < kRsPairRows; ++k) {
-    j[k] = rs_target(corr, n, P1, first + k, len1, len2);
-    mine += j[k] >= 0 ? 1 : 0;
+// The row source of the compaction: a row's key is its target in Y.
+struct RansacPairs {
+  using Record = RansacRecord;
+  const float *X, *Y;
+  const int64_t *corr, *lengths1, *lengths2;
+  int P1, P2, len1, len2;
+  __device__ __forceinline__ void enter(int n) {
+    len1 = clamped_length(lengths1, n, P1);
+    len2 = clamped_length(lengths2, n, P2);
   }
-  return mine;
-}
-
-__global__ __launch_bounds__(kRsBlock) void ransac_pair_count_kernel(
-    const int64_t* __restrict__ corr, const int64_t* __restrict__ lengths1, const int64_t* __restrict__ lengths2,
-    int P1, int P2, int* __restrict__ tile_pairs) {
-  __shared__ int s_wsum[kRsWaves];
-  const int n = blockIdx.y;
-  int j[kRsPairRows], total;
-  const int mine = rs_tile_targets(corr, n, P1, rs_length(lengths1, n, P1), rs_length(lengths2, n, P2), j);
-  block_exclusive_sum<kRsWaves>(mine, s_wsum, total);
-  if (threadIdx.x == 0) tile_pairs[(int64_t)n * gridDim.x + blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kRsBlock) void ransac_pairs_kernel(
-    const float* __restrict__ X, const float* __restrict__ Y, const int64_t* __restrict__ corr,
-    const int64_t* __restrict__ lengths1, const int64_t* __restrict__ lengths2, int P1, int P2,
-    const int* __restrict__ tile_pairs, RansacRecord* __restrict__ records, int* __restrict__ num_pairs) {
-  __shared__ int s_wsum[kRsWaves];
-  const int n = blockIdx.y, tile = blockIdx.x, tiles = gridDim.x;
-  const float* __restrict__ xs = X + (int64_t)n * P1 * 3;
-  const float* __restrict__ ys = Y + (int64_t)n * P2 * 3;
-  float4* __restrict__ out = (float4*)(records + (int64_t)n * P1);
-  int base = 0;
-  for (int t = 0; t < tile; ++t) base += tile_pairs[(int64_t)n * tiles + t];  // (uniform: scalar loads)
-  int j[kRsPairRows], total;
-  const int mine = rs_tile_targets(corr, n, P1, rs_length(lengths1, n, P1), rs_length(lengths2, n, P2), j);
-  int at = base + block_exclusive_sum<kRsWaves>(mine, s_wsum, total);
-  const int first = tile * kRsPairTile + (int)threadIdx.x * kRsPairRows;
-#pragma unroll
-  for (int k = 0; k < kRsPairRows; ++k) {
-    if (j[k] < 0) continue;
-    const int64_t i = first + k, t = j[k];
-    const float x0 = xs[i * 3], x1 = xs[i * 3 + 1], x2 = xs[i * 3 + 2];
-    const float y0 = ys[t * 3], y1 = ys[t * 3 + 1], y2 = ys[t * 3 + 2];
-    out[2 * (int64_t)at] = make_float4(x0, x1, x2, y0);
-    out[2 * (int64_t)at + 1] = make_float4(y1, y2, __int_as_float((int)i), 0.0f);
-    ++at;
+  __device__ __forceinline__ int key(int n, int i) const { return rs_target(corr, n, P1, i, len1, len2); }
+  __device__ __forceinline__ void store(RansacRecord* __restrict__ out, int at, int n, int i, int j) const {
+    const float* __restrict__ x = X + (int64_t)n * P1 * 3 + (int64_t)i * 3;
+    const float* __restrict__ y = Y + (int64_t)n * P2 * 3 + (int64_t)j * 3;
+    const float x0 = x[0], x1 = x[1], x2 = x[2], y0 = y[0], y1 = y[1], y2 = y[2];
+    ((float4*)out)[2 * (int64_t)at] = make_float4(x0, x1, x2, y0);
+    ((float4*)out)[2 * (int64_t)at + 1] = make_float4(y1, y2, __int_as_float(i), 0.0f);
   }
-  if (tile == tiles - 1 && threadIdx.x == 0) num_pairs[n] = base + total;
-}
+};
 
 // ---------------------------------------------------------------------------------------------------- 2. hypotheses
-__global__ __launch_bounds__(kRsBlock) void ransac_hypotheses_kernel(
+__global__ __launch_bounds__(kCsBlock) void ransac_hypotheses_kernel(
     const float* __restrict__ X, const float* __restrict__ Y, const int64_t* __restrict__ corr,
     const int64_t* __restrict__ lengths1, const int64_t* __restrict__ lengths2,
     const int64_t* __restrict__ samples_in, int P1, int P2, int H, int64_t seed, int64_t first_cloud, float q,
@@ -125,14 +77,14 @@ __global__ __launch_bounds__(kRsBlock) void ransac_hypotheses_kernel(
     float* __restrict__ hyp_R, float* __restrict__ hyp_T, float* __restrict__ hyp_s,
     int64_t* __restrict__ samples_out) {
   const int n = blockIdx.y;
-  const int h = blockIdx.x * kRsBlock + (int)threadIdx.x;
+  const int h = blockIdx.x * kCsBlock + (int)threadIdx.x;
   if (h >= H) return;
   const int64_t slot = (int64_t)n * H + h;
   float x[3][3], y[3][3];
   int64_t rows[3] = {-1, -1, -1};
   bool valid;
   if (samples_in != nullptr) {
-    const int len1 = rs_length(lengths1, n, P1), len2 = rs_length(lengths2, n, P2);
+    const int len1 = clamped_length(lengths1, n, P1), len2 = clamped_length(lengths2, n, P2);
     valid = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -204,7 +156,7 @@ __device__ __forceinline__ void rs_load_transform(const float* __restrict__ R, c
 // LDS = false: the scalar path.  LDS = true (POINTOPS_DEBUG="ransac_lds=1", the A/B of DESIGN 4.8): the workgroup
 // copies its chunk into an LDS tile and every lane reads the same address (a broadcast).  The results are the same.
 template <bool LDS>
-__global__ __launch_bounds__(kRsBlock) void ransac_score_kernel(
+__global__ __launch_bounds__(kCsBlock) void ransac_score_kernel(
     const RansacRecord* __restrict__ records, const int* __restrict__ num_pairs, const float* __restrict__ ws_R,
     const float* __restrict__ ws_T, const float* __restrict__ ws_s, const int* __restrict__ ws_valid, int P1, int H,
     int S, float thr2, int* __restrict__ partials) {
@@ -216,7 +168,7 @@ __global__ __launch_bounds__(kRsBlock) void ransac_score_kernel(
   const int end = min(beg + kRansacChunk, M);
   const RansacRecord* __restrict__ rec = records + (int64_t)n * P1;
   if constexpr (LDS) {
-    static_assert(kRansacChunk == kRsBlock, "one record per thread");
+    static_assert(kRansacChunk == kCsBlock, "one record per thread");
     if (beg + (int)threadIdx.x < end) {
       const float4* __restrict__ src = (const float4*)(rec + beg + threadIdx.x);
       s_rec[2 * threadIdx.x] = src[0];
@@ -224,7 +176,7 @@ __global__ __launch_bounds__(kRsBlock) void ransac_score_kernel(
     }
     __syncthreads();
   }
-  const int h = blockIdx.x * kRsBlock + (int)threadIdx.x;
+  const int h = blockIdx.x * kCsBlock + (int)threadIdx.x;
   const bool valid = h < H && ws_valid[(int64_t)n * H + h] != 0;
   int* __restrict__ out = partials + ((int64_t)n * S + chunk) * H;
   if (__ballot(valid) == 0ull) {  // the whole wave is invalid
@@ -251,44 +203,13 @@ __global__ __launch_bounds__(kRsBlock) void ransac_score_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------- 4. selection
-// One lane per (cloud, hypothesis): the sum of its chunk partials (coalesced over the hypotheses), the optional
-// `counts` output, and the tile's largest key -- count in the high word, the inverted index in the low one, so that
-// the maximum is the largest count at the lowest index; 0 = no valid hypothesis (a valid one has a low word >= 1).
-__global__ __launch_bounds__(kRsBlock) void ransac_count_kernel(
-    const int* __restrict__ num_pairs, const int* __restrict__ partials, const int* __restrict__ ws_valid, int H, int S,
-    int* __restrict__ counts, unsigned long long* __restrict__ tile_keys) {
-  __shared__ unsigned long long s_key[kRsWaves];
-  const int n = blockIdx.y;
-  const int live = (num_pairs[n] + kRansacChunk - 1) / kRansacChunk;  // <= S
-  const int h = blockIdx.x * kRsBlock + (int)threadIdx.x;
-  unsigned long long key = 0ull;
-  if (h < H) {
-    int c = -1;
-    if (ws_valid[(int64_t)n * H + h] != 0) {
-      c = 0;
-      for (int k = 0; k < live; ++k) c += partials[((int64_t)n * S + k) * H + h];
-      key = ((unsigned long long)(uint32_t)c << 32) | (uint32_t)(0xffffffffu - (uint32_t)h);
-    }
-    if (counts != nullptr) counts[(int64_t)n * H + h] = c;
-  }
-  key = rs_block_max(key, s_key);
-  if (threadIdx.x == 0) tile_keys[(int64_t)n * gridDim.x + blockIdx.x] = key;
-}
-
-__global__ __launch_bounds__(kRsBlock) void ransac_select_kernel(
+__global__ __launch_bounds__(kCsBlock) void ransac_select_kernel(
     const unsigned long long* __restrict__ tile_keys, int tiles, const float* __restrict__ ws_R,
     const float* __restrict__ ws_T, const float* __restrict__ ws_s, int H, int64_t* __restrict__ best,
     float* __restrict__ cand_R, float* __restrict__ cand_T, float* __restrict__ cand_s) {
-  __shared__ unsigned long long s_key[kRsWaves];
   const int n = blockIdx.x;
-  unsigned long long key = 0ull;
-  for (int t = threadIdx.x; t < tiles; t += kRsBlock) {
-    const unsigned long long o = tile_keys[(int64_t)n * tiles + t];
-    key = o > key ? o : key;
-  }
-  key = rs_block_max(key, s_key);
+  const int64_t b = cs_best(tile_keys, tiles, n);
   if (threadIdx.x != 0) return;
-  const int64_t b = key == 0ull ? -1 : (int64_t)(0xffffffffu - (uint32_t)(key & 0xffffffffull));
   best[n] = b;
   const int64_t slot = (int64_t)n * H + (b < 0 ? 0 : b);
   cand_s[n] = b < 0 ? 1.0f : ws_s[slot];
@@ -302,79 +223,50 @@ __global__ __launch_bounds__(kRsBlock) void ransac_select_kernel(
 
 // ---------------------------------------------------------------------------------------------------- 5. evaluation
 // Mask (one byte per row of X), count and sum of d2 over the inliers of the candidate transform of every cloud.
-__global__ __launch_bounds__(kRsBlock) void ransac_evaluate_kernel(
+__global__ __launch_bounds__(kCsBlock) void ransac_evaluate_kernel(
     const float* __restrict__ X, const float* __restrict__ Y, const int64_t* __restrict__ corr,
     const int64_t* __restrict__ lengths1, const int64_t* __restrict__ lengths2, const int64_t* __restrict__ best,
     const float* __restrict__ cand_R, const float* __restrict__ cand_T, const float* __restrict__ cand_s, int P1,
     int P2, float thr2, uint8_t* __restrict__ cand_mask, double* __restrict__ part_sum, int* __restrict__ part_count) {
-  __shared__ double s_sum[kRsWaves];
-  __shared__ int s_cnt[kRsWaves];
   const int n = blockIdx.y, nb = gridDim.x;
-  const int len1 = rs_length(lengths1, n, P1), len2 = rs_length(lengths2, n, P2);
+  const int len1 = clamped_length(lengths1, n, P1), len2 = clamped_length(lengths2, n, P2);
   const bool none = best[n] < 0;
   float A[3][3], T[3];
   rs_load_transform(cand_R, cand_T, cand_s, n, A, T);
   const float* __restrict__ xs = X + (int64_t)n * P1 * 3;
   const float* __restrict__ ys = Y + (int64_t)n * P2 * 3;
-  double sum = 0.0;
+  double sum[1] = {0.0};
   int cnt = 0;
-  for (int i = blockIdx.x * kRsBlock + (int)threadIdx.x; i < P1; i += nb * kRsBlock) {
+  for (int i = blockIdx.x * kCsBlock + (int)threadIdx.x; i < P1; i += nb * kCsBlock) {
     const int j = none ? -1 : rs_target(corr, n, P1, i, len1, len2);
     bool in = false;
     if (j >= 0) {
       const float d2 = rh_residual(A, T, xs[(int64_t)i * 3], xs[(int64_t)i * 3 + 1], xs[(int64_t)i * 3 + 2],
                                    ys[(int64_t)j * 3], ys[(int64_t)j * 3 + 1], ys[(int64_t)j * 3 + 2]);
       in = d2 <= thr2;
-      if (in) sum += (double)d2;
+      if (in) sum[0] += (double)d2;
     }
     cnt += in ? 1 : 0;
     cand_mask[(int64_t)n * P1 + i] = in ? 1 : 0;
   }
-  sum = wave_sum(sum);
-  cnt = wave_sum(cnt);
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-    s_sum[threadIdx.x / kWave] = sum;
-    s_cnt[threadIdx.x / kWave] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kRsWaves; ++w) {
-      sum += s_sum[w];
-      cnt += s_cnt[w];
-    }
-    part_sum[(int64_t)n * nb + blockIdx.x] = sum;
-    part_count[(int64_t)n * nb + blockIdx.x] = cnt;
-  }
+  const int64_t slot = (int64_t)n * nb + blockIdx.x;
+  cs_block_partials(sum, cnt, nb, part_sum + slot, part_count + slot);
 }
 
-// One block per cloud: the candidate's count and rmse from the block partials (ascending), the accept rule, and -- on
-// acceptance -- the public transform, mask, count and rmse, and the 0/1 weights of the next fit.  `first`: the
-// winner's own evaluation, always accepted.  stopped[n] != 0: a fit was rejected (or no hypothesis is valid) and the
-// cloud keeps what it has.
-__global__ __launch_bounds__(kRsBlock) void ransac_finish_kernel(
+// One block per cloud: the accept rule and -- on acceptance -- the public transform, mask, count and rmse, and the 0/1
+// weights of the next fit.
+__global__ __launch_bounds__(kCsBlock) void ransac_finish_kernel(
     const double* __restrict__ part_sum, const int* __restrict__ part_count, int nb, int first,
     const int64_t* __restrict__ best, const float* __restrict__ cand_R, const float* __restrict__ cand_T,
     const float* __restrict__ cand_s, const uint8_t* __restrict__ cand_mask, int P1, int* __restrict__ stopped,
     float* __restrict__ R, float* __restrict__ T, float* __restrict__ s, uint8_t* __restrict__ mask,
     float* __restrict__ weights, int64_t* __restrict__ num_inliers, float* __restrict__ rmse) {
   const int n = blockIdx.x;
-  double sum = 0.0;
-  int cnt = 0;
-  for (int b = 0; b < nb; ++b) {  // (every thread: the decision is workgroup-uniform)
-    sum += part_sum[(int64_t)n * nb + b];
-    cnt += part_count[(int64_t)n * nb + b];
-  }
-  const bool accept = first ? true : (stopped[n] == 0 && (int64_t)cnt >= num_inliers[n]);
-  __syncthreads();  // every thread has read stopped / num_inliers before thread 0 writes them
-  if (!accept) {
-    if (threadIdx.x == 0) stopped[n] = 1;
-    return;
-  }
+  int cnt;
+  double sum;
+  if (!cs_accept(part_sum + (int64_t)n * nb, part_count, nb, n, first, true, stopped, num_inliers, cnt, sum)) return;
   if (threadIdx.x == 0) {
-    if (first) stopped[n] = best[n] < 0 ? 1 : 0;
-    num_inliers[n] = cnt;
-    rmse[n] = (float)sqrt(sum / (double)(cnt > 1 ? cnt : 1));
+    cs_publish(n, first, best, cnt, sum, stopped, num_inliers, rmse);
     s[n] = cand_s[n];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -387,14 +279,14 @@ __global__ __launch_bounds__(kRsBlock) void ransac_finish_kernel(
     const uchar4* __restrict__ src = (const uchar4*)(cand_mask + (int64_t)n * P1);
     uchar4* __restrict__ dst = (uchar4*)(mask + (int64_t)n * P1);
     float4* __restrict__ w = (float4*)(weights + (int64_t)n * P1);
-    for (int i = threadIdx.x; i < P1 / 4; i += kRsBlock) {
+    for (int i = threadIdx.x; i < P1 / 4; i += kCsBlock) {
       const uchar4 m = src[i];
       dst[i] = m;
       w[i] = make_float4(m.x ? 1.0f : 0.0f, m.y ? 1.0f : 0.0f, m.z ? 1.0f : 0.0f, m.w ? 1.0f : 0.0f);
     }
     return;
   }
-  for (int i = threadIdx.x; i < P1; i += kRsBlock) {
+  for (int i = threadIdx.x; i < P1; i += kCsBlock) {
     const uint8_t m = cand_mask[(int64_t)n * P1 + i];
     mask[(int64_t)n * P1 + i] = m;
     weights[(int64_t)n * P1 + i] = m ? 1.0f : 0.0f;
@@ -402,20 +294,13 @@ __global__ __launch_bounds__(kRsBlock) void ransac_finish_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
-struct RansacLayout {
+struct RansacLayout : CsLayout {  // (num_valid: the pairs of a cloud)
   RansacRecord* records;  // (N, P1)
-  int* num_pairs;         // (N,)
-  int* tile_pairs;        // (N, ceil(P1 / 2048))
   float *hyp_R, *hyp_T, *hyp_s;  // (N, H, 9 | 3 | 1)
-  int* hyp_valid;         // (N, H)
-  int* partials;          // (N, S, H)
-  unsigned long long* tile_keys;  // (N, ceil(H / 256))
   float *cand_R, *cand_T, *cand_s;  // (N, 9 | 3 | 1)
   uint8_t* cand_mask;     // (N, P1)
   float* weights;         // (N, P1)
   double* part_sum;       // (N, nb)
-  int* part_count;        // (N, nb)
-  int* stopped;           // (N,)
   void* alignment;        // pointops_points_alignment's own
   size_t alignment_bytes;
   size_t bytes;
@@ -424,25 +309,18 @@ struct RansacLayout {
 static RansacLayout ransac_layout(void* ws, int64_t N, int64_t P1, int64_t H) {
   Carver c(ws);
   RansacLayout l;
+  static_cast<CsLayout&>(l) = cs_layout(c, N, P1, H, kRansacChunk);
   const size_t n = (size_t)N, p = (size_t)P1, h = (size_t)H;
-  const size_t S = (size_t)ceil_div(P1, kRansacChunk), nb = (size_t)rs_eval_blocks(P1);
   l.records = (RansacRecord*)c.take(sizeof(RansacRecord) * n * p);
-  l.num_pairs = (int*)c.take(sizeof(int) * n);
-  l.tile_pairs = (int*)c.take(sizeof(int) * n * (size_t)rs_pair_tiles(P1));
   l.hyp_R = (float*)c.take(sizeof(float) * n * h * 9);
   l.hyp_T = (float*)c.take(sizeof(float) * n * h * 3);
   l.hyp_s = (float*)c.take(sizeof(float) * n * h);
-  l.hyp_valid = (int*)c.take(sizeof(int) * n * h);
-  l.partials = (int*)c.take(sizeof(int) * n * S * h);
-  l.tile_keys = (unsigned long long*)c.take(sizeof(unsigned long long) * n * (size_t)ceil_div(H, kRsBlock));
   l.cand_R = (float*)c.take(sizeof(float) * n * 9);
   l.cand_T = (float*)c.take(sizeof(float) * n * 3);
   l.cand_s = (float*)c.take(sizeof(float) * n);
   l.cand_mask = (uint8_t*)c.take(n * p);
   l.weights = (float*)c.take(sizeof(float) * n * p);
-  l.part_sum = (double*)c.take(sizeof(double) * n * nb);
-  l.part_count = (int*)c.take(sizeof(int) * n * nb);
-  l.stopped = (int*)c.take(sizeof(int) * n);
+  l.part_sum = (double*)c.take(sizeof(double) * n * (size_t)cs_eval_blocks(P1));
   l.alignment_bytes = pointops_points_alignment_workspace_bytes(N, P1, 3);
   l.alignment = c.take(l.alignment_bytes);
   l.bytes = c.off;
@@ -450,9 +328,7 @@ static RansacLayout ransac_layout(void* ws, int64_t N, int64_t P1, int64_t H) {
 }
 
 static bool ransac_shape_ok(int64_t N, int64_t P1, int64_t P2, int64_t H) {
-  // (the chunks of a cloud are a grid's y coordinate, the tiles of 256 hypotheses its x, the cloud its z)
-  return N >= 0 && N < 65536 && P1 >= 0 && P1 <= 65535LL * kRansacChunk && P2 >= 0 && P2 < (1LL << 30) && H >= 1 &&
-         H <= (1LL << 24);
+  return cs_shape_ok(N, P1, H, kRansacChunk) && P2 >= 0 && P2 < (1LL << 30);
 }
 
 }  // namespace pointops
@@ -490,29 +366,24 @@ extern "C" int pointops_ransac_alignment(
   const float thr2 = inlier_threshold * inlier_threshold;
   const float q = edge_length_ratio * edge_length_ratio;
   const int edge_test = (!estimate_scale && edge_length_ratio > 0.0f) ? 1 : 0;
-  const unsigned tiles = (unsigned)ceil_div(H, kRsBlock), S = (unsigned)ceil_div(P1, kRansacChunk);
-  const int nb = rs_eval_blocks(P1);
+  const CsGrid g(N, P1, H, kRansacChunk);
+  const dim3 block(kCsBlock);
 
-  const dim3 pair_grid((unsigned)rs_pair_tiles(P1), (unsigned)N);
-  hipLaunchKernelGGL(ransac_pair_count_kernel, pair_grid, dim3(kRsBlock), 0, stream, corr, lengths1, lengths2, (int)P1,
-                     (int)P2, l.tile_pairs);
-  hipLaunchKernelGGL(ransac_pairs_kernel, pair_grid, dim3(kRsBlock), 0, stream, X, Y, corr, lengths1, lengths2, (int)P1,
-                     (int)P2, (const int*)l.tile_pairs, l.records, l.num_pairs);
-  hipLaunchKernelGGL(ransac_hypotheses_kernel, dim3(tiles, (unsigned)N), dim3(kRsBlock), 0, stream, X, Y, corr,
-                     lengths1, lengths2, samples_in, (int)P1, (int)P2, (int)H, seed, first_cloud, q, edge_test,
-                     estimate_scale, (const RansacRecord*)l.records, (const int*)l.num_pairs, l.hyp_R, l.hyp_T, l.hyp_s,
-                     l.hyp_valid, hyp_R, hyp_T, hyp_s, samples_out);
-  if (S > 0) {
+  cs_launch_compact(RansacPairs{X, Y, corr, lengths1, lengths2, (int)P1, (int)P2, 0, 0}, g, l, P1, l.records, stream);
+  hipLaunchKernelGGL(ransac_hypotheses_kernel, g.hyp, block, 0, stream, X, Y, corr, lengths1, lengths2, samples_in,
+                     (int)P1, (int)P2, (int)H, seed, first_cloud, q, edge_test, estimate_scale,
+                     (const RansacRecord*)l.records, (const int*)l.num_valid, l.hyp_R, l.hyp_T, l.hyp_s, l.hyp_valid,
+                     hyp_R, hyp_T, hyp_s, samples_out);
+  if (g.S > 0) {
     auto* score = debug_knob("ransac_lds", 0) ? ransac_score_kernel<true> : ransac_score_kernel<false>;
-    hipLaunchKernelGGL(score, dim3(tiles, S, (unsigned)N), dim3(kRsBlock), 0, stream, (const RansacRecord*)l.records,
-                       (const int*)l.num_pairs, (const float*)l.hyp_R, (const float*)l.hyp_T, (const float*)l.hyp_s,
-                       (const int*)l.hyp_valid, (int)P1, (int)H, (int)S, thr2, l.partials);
+    hipLaunchKernelGGL(score, dim3(g.tiles, g.S, (unsigned)N), block, 0, stream, (const RansacRecord*)l.records,
+                       (const int*)l.num_valid, (const float*)l.hyp_R, (const float*)l.hyp_T, (const float*)l.hyp_s,
+                       (const int*)l.hyp_valid, (int)P1, (int)H, (int)g.S, thr2, l.partials);
   }
-  hipLaunchKernelGGL(ransac_count_kernel, dim3(tiles, (unsigned)N), dim3(kRsBlock), 0, stream, (const int*)l.num_pairs,
-                     (const int*)l.partials, (const int*)l.hyp_valid, (int)H, (int)S, counts, l.tile_keys);
-  hipLaunchKernelGGL(ransac_select_kernel, dim3((unsigned)N), dim3(kRsBlock), 0, stream,
-                     (const unsigned long long*)l.tile_keys, (int)tiles, (const float*)l.hyp_R, (const float*)l.hyp_T,
-                     (const float*)l.hyp_s, (int)H, best, l.cand_R, l.cand_T, l.cand_s);
+  cs_launch_count<kRansacChunk>(g, l, H, counts, stream);
+  hipLaunchKernelGGL(ransac_select_kernel, g.cloud, block, 0, stream, (const unsigned long long*)l.tile_keys,
+                     (int)g.tiles, (const float*)l.hyp_R, (const float*)l.hyp_T, (const float*)l.hyp_s, (int)H, best,
+                     l.cand_R, l.cand_T, l.cand_s);
   int rc = check_launch("ransac_alignment");
   const int refits = P1 == 0 ? 0 : refine_steps;  // (no row, nothing to refit)
   for (int step = 0; step <= refits && rc == POINTOPS_OK; ++step) {
@@ -521,11 +392,11 @@ extern "C" int pointops_ransac_alignment(
                                      l.cand_T, l.cand_s, nullptr, nullptr, l.alignment, l.alignment_bytes, stream_);
       if (rc != POINTOPS_OK) return rc;
     }
-    hipLaunchKernelGGL(ransac_evaluate_kernel, dim3((unsigned)nb, (unsigned)N), dim3(kRsBlock), 0, stream, X, Y, corr,
-                       lengths1, lengths2, (const int64_t*)best, (const float*)l.cand_R, (const float*)l.cand_T,
-                       (const float*)l.cand_s, (int)P1, (int)P2, thr2, l.cand_mask, l.part_sum, l.part_count);
-    hipLaunchKernelGGL(ransac_finish_kernel, dim3((unsigned)N), dim3(kRsBlock), 0, stream, (const double*)l.part_sum,
-                       (const int*)l.part_count, nb, step == 0 ? 1 : 0, (const int64_t*)best, (const float*)l.cand_R,
+    hipLaunchKernelGGL(ransac_evaluate_kernel, g.eval, block, 0, stream, X, Y, corr, lengths1, lengths2,
+                       (const int64_t*)best, (const float*)l.cand_R, (const float*)l.cand_T, (const float*)l.cand_s,
+                       (int)P1, (int)P2, thr2, l.cand_mask, l.part_sum, l.part_count);
+    hipLaunchKernelGGL(ransac_finish_kernel, g.cloud, block, 0, stream, (const double*)l.part_sum,
+                       (const int*)l.part_count, g.nb, step == 0 ? 1 : 0, (const int64_t*)best, (const float*)l.cand_R,
                        (const float*)l.cand_T, (const float*)l.cand_s, (const uint8_t*)l.cand_mask, (int)P1, l.stopped,
                        R, T, s, inlier_mask, l.weights, num_inliers, rmse);
     rc = check_launch("ransac_alignment");

@@ -17,6 +17,7 @@ import torch
 
 from .. import _C_plane
 from ..structures.pointclouds import Pointclouds
+from ._consensus import _cloud, _sampling
 
 PlaneSegmentation = namedtuple("PlaneSegmentation", "planes inliers num_inliers rmse best counts hypotheses samples")
 PlaneSet = namedtuple("PlaneSet", "planes labels num_inliers")
@@ -29,34 +30,18 @@ def _f32(v: float) -> float:
 
 def _arguments(points, distance_threshold, num_hypotheses, refine_steps, seed, mask, axis, max_angle_deg, samples):
     """Validation shared by the two public functions -> (points, lengths, mask, axis32, cos32, H, refine_steps, seed)."""
-    lengths = None
-    if isinstance(points, Pointclouds):
-        points, lengths = points.points_padded(), points.num_points_per_cloud()
-    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[2] != 3:
-        raise ValueError("points must be a padded tensor of shape (N, P, 3) or a Pointclouds")
-    if points.dtype != torch.float32:
-        raise ValueError(f"points must be float32, got {points.dtype}")
+    points, lengths = _cloud(points, "points")
     N, P = points.shape[0], points.shape[1]
     if mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.bool or mask.shape != (N, P)):
         raise ValueError("mask must be a bool tensor of shape (N, P)")
-    if samples is not None:
-        if not torch.is_tensor(samples) or samples.dtype != torch.int64 or samples.dim() != 3 \
-                or samples.shape[0] != N or samples.shape[2] != 3:
-            raise ValueError("samples must be an int64 tensor of shape (N, H, 3)")
-        num_hypotheses = samples.shape[1]
-    num_hypotheses, refine_steps, seed = int(num_hypotheses), int(refine_steps), int(seed)
-    if not 1 <= num_hypotheses <= _C_plane.PLANE_MAX_HYPOTHESES:
-        raise ValueError(f"num_hypotheses must be in 1..{_C_plane.PLANE_MAX_HYPOTHESES}, got {num_hypotheses}")
+    num_hypotheses, refine_steps, seed = _sampling(samples, N, num_hypotheses, refine_steps, seed,
+                                                   _C_plane.PLANE_MAX_HYPOTHESES)
     try:
         thr = _f32(float(distance_threshold))
     except OverflowError:
         thr = math.inf
     if not (math.isfinite(thr) and thr >= 0.0):
         raise ValueError(f"distance_threshold must be finite and >= 0 in float32, got {distance_threshold}")
-    if refine_steps < 0:
-        raise ValueError(f"refine_steps must be >= 0, got {refine_steps}")
-    if not 0 <= seed < 2 ** 63:
-        raise ValueError(f"seed must be in 0..2^63-1, got {seed}")
     if (axis is None) != (max_angle_deg is None):
         raise ValueError("axis and max_angle_deg come together: pass both or neither")
     axis32 = cos32 = None
@@ -70,7 +55,7 @@ def _arguments(points, distance_threshold, num_hypotheses, refine_steps, seed, m
         axis32 = tuple(_f32(v / norm) for v in a)
         # (90 degrees admits every normal: the rounded cosine of pi / 2 would throw the exactly perpendicular ones out)
         cos32 = 0.0 if float(max_angle_deg) >= 90.0 else min(max(_f32(math.cos(math.radians(float(max_angle_deg)))), 0.0), 1.0)
-    return points.detach(), lengths, mask, axis32, cos32, thr, num_hypotheses, refine_steps, seed
+    return points, lengths, mask, axis32, cos32, thr, num_hypotheses, refine_steps, seed
 
 
 @torch.compiler.disable

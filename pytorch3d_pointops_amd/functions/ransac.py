@@ -17,21 +17,10 @@ import torch
 
 from .. import _C_ransac
 from ..structures.pointclouds import Pointclouds
+from ._consensus import _cloud, _sampling
 from .points_alignment import SimilarityTransform
 
 RansacSolution = namedtuple("RansacSolution", "RTs inliers num_inliers rmse best counts hypotheses samples")
-
-
-def _cloud(points, name: str):
-    """(padded (N,P,3) float32 tensor, lengths or None) of a tensor or a Pointclouds."""
-    lengths = None
-    if isinstance(points, Pointclouds):
-        points, lengths = points.points_padded(), points.num_points_per_cloud()
-    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[2] != 3:
-        raise ValueError(f"{name} must be a padded tensor of shape (N, P, 3) or a Pointclouds")
-    if points.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {points.dtype}")
-    return points.detach(), lengths
 
 
 @torch.compiler.disable
@@ -71,22 +60,12 @@ def ransac_alignment(X: Union[torch.Tensor, Pointclouds], Y: Union[torch.Tensor,
             raise ValueError("corr=None matches row i to row i: X and Y must have the same number of rows")
     elif not torch.is_tensor(corr) or corr.dtype != torch.int64 or corr.shape != (N, P1):
         raise ValueError("corr must be an int64 tensor of shape (N, P1)")
-    if samples is not None:
-        if not torch.is_tensor(samples) or samples.dtype != torch.int64 or samples.dim() != 3 \
-                or samples.shape[0] != N or samples.shape[2] != 3:
-            raise ValueError("samples must be an int64 tensor of shape (N, H, 3)")
-        num_hypotheses = samples.shape[1]
-    num_hypotheses, refine_steps, seed = int(num_hypotheses), int(refine_steps), int(seed)
-    if not 1 <= num_hypotheses <= _C_ransac.RANSAC_MAX_HYPOTHESES:
-        raise ValueError(f"num_hypotheses must be in 1..{_C_ransac.RANSAC_MAX_HYPOTHESES}, got {num_hypotheses}")
+    num_hypotheses, refine_steps, seed = _sampling(samples, N, num_hypotheses, refine_steps, seed,
+                                                   _C_ransac.RANSAC_MAX_HYPOTHESES)
     if not float(inlier_threshold) >= 0.0:
         raise ValueError(f"inlier_threshold must be >= 0, got {inlier_threshold}")
     if not 0.0 <= float(edge_length_ratio) <= 1.0:
         raise ValueError(f"edge_length_ratio must be in [0, 1], got {edge_length_ratio}")
-    if refine_steps < 0:
-        raise ValueError(f"refine_steps must be >= 0, got {refine_steps}")
-    if not 0 <= seed < 2 ** 63:
-        raise ValueError(f"seed must be in 0..2^63-1, got {seed}")
     with torch.no_grad():
         R, T, s, mask, num_inliers, rmse, best, counts, hyp_R, hyp_T, hyp_s, drawn = _C_ransac.ransac_alignment(
             X, Y, corr, lengths1, lengths2, samples, num_hypotheses, seed, inlier_threshold, edge_length_ratio,

@@ -326,6 +326,11 @@ SCENES = {
     "p2047": dict(seed=5, P=2047, ratio=0.4, H=256),  # the compaction walks 2048 rows per step
     "p2048": dict(seed=6, P=2048, ratio=0.4, H=256),
     "p2049": dict(seed=7, P=2049, ratio=0.4, H=256),
+    # three tiles: the third adds the counts of two.  The mask switches rows off in all of them: the third tile is row
+    # 4096 alone, valid in cloud 0 (its record follows those of both earlier tiles) and masked out in cloud 1
+    "p4097": dict(seed=52, P=4097, ratio=0.4, H=256, N=2, masked=3600),
+    # 33 tiles, and the first P at which the evaluation's 32 blocks walk their rows twice
+    "p65537": dict(seed=60, P=65537, ratio=0.5, H=64, refine_steps=1),
     "chunk-1": dict(seed=8, P=CHUNK + 90, masked=CHUNK - 1, ratio=0.5, H=256),
     "chunk": dict(seed=9, P=CHUNK + 90, masked=CHUNK, ratio=0.5, H=256),
     "chunk+1": dict(seed=10, P=CHUNK + 90, masked=CHUNK + 1, ratio=0.5, H=256),

@@ -352,6 +352,10 @@ SCENES = {
     "p2047": dict(seed=16, P1=2047, inlier_ratio=0.4, H=256),  # the compaction walks 2048 rows per step
     "p2048": dict(seed=17, P1=2048, inlier_ratio=0.4, H=256),
     "p2049": dict(seed=18, P1=2049, inlier_ratio=0.4, H=256),
+    # three tiles: the third (row 4096 alone, a valid pair) adds the counts of two; 81 rows without a match in those
+    "p4097": dict(seed=40, P1=4097, inlier_ratio=0.4, H=256),
+    # 33 tiles, and the first P1 at which the evaluation's 32 blocks walk their rows twice
+    "p65537": dict(seed=60, P1=65537, inlier_ratio=0.5, H=64, refine_steps=1),
     "h1": dict(seed=12, P1=300, inlier_ratio=0.5, H=1, planted=False),
     "h63": dict(seed=13, P1=300, inlier_ratio=0.5, H=63, planted=False),
     "h64": dict(seed=14, P1=300, inlier_ratio=0.5, H=64, planted=False),
