@@ -632,6 +632,84 @@ int pointops_voxel_downsample(const float* points, const int64_t* lengths, const
                               int64_t* first_index, int64_t* coords, float* centroids, float* pooled, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/*
+ * Outlier removal: the stray returns of a real sensor taken out before anything else looks at the cloud -- Open3D's
+ * remove_radius_outlier / remove_statistical_outlier, PCL's RadiusOutlierRemoval / StatisticalOutlierRemoval -- device
+ * half of functions/filters.py (csrc/filters.hip).  The semantics are this library's own; all fp32 and fp64 arithmetic
+ * is unfused and in the order written.  Three entries: the two filters and the compaction both end with.
+ *
+ * COMPACTION (pointops_mask_compact, and the last step of both filters).
+ *   mask (N,P) one byte per row, a row is KEPT when its byte is not 0.
+ *   1. index[n, 0 .. k_n) = the kept rows of cloud n in ascending order, index[n, k_n .. P) = -1; num_kept[n] = k_n.
+ *   A stable two-level scan without atomics: kept rows counted per block of 1024 rows, the counts of a cloud scanned
+ *   by one workgroup, every block scattering behind its offset.  It needs no workspace: until its last launch the
+ *   block offsets live in the upper halves of index[n, 0 .. ceil(P / 1024)), which that launch overwrites.
+ *   index (N,P) int64 and num_kept (N,) int64 are fully written.  0 <= N < 65536 (a bigger batch goes in slices),
+ *   0 <= P < 2^30: anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing; P == 0 writes
+ *   num_kept = 0.
+ *
+ * RADIUS FILTER (pointops_radius_outlier): keep the rows with enough company.
+ *   points (N,P,D) fp32, D in 1..3; lengths (N,) or NULL (= P; clamped into [0,P]).  Per cloud n:
+ *   1. r2 = radius * radius (fp32).  d2(i,j) = (dx*dx + dy*dy) + dz*dz over the D coordinates in fp32, dx = x_i - x_j:
+ *      ball query's and pointops_cluster_dbscan's expression.
+ *   2. c_i = the number of rows j != i, j < lengths[n], with d2(i,j) < r2, for every row i < lengths[n].
+ *   3. mask[n,i] = 1 iff c_i >= min_neighbors.  Rows at or past the length: mask 0 (counts 0).
+ *   So mask equals pointops_cluster_dbscan's core_mask at eps = radius, min_points = min_neighbors + 1 on every row
+ *   whose coordinates are finite (a row with a non-finite coordinate has c_i = 0 here and no neighbours there).
+ *   4. index, num_kept: the COMPACTION of mask.
+ *   One lane per point walks the 3x3x3 cube of a grid with cells at least 1.001 radius wide under ball query's
+ *   certificate (csrc/radius_walk.h), and stops as soon as c_i reaches min_neighbors -- unless counts is given: then
+ *   it finishes and writes the exact c_i.  Clouds too small for a grid, refused grids and lanes without the
+ *   certificate walk all pairs: which path a lane takes never changes a result.
+ *   Outputs: mask (N,P) one byte 0/1 per row, index (N,P) int64, num_kept (N,) int64; optional (NULL skips it) counts
+ *   (N,P) int32.  Every output is fully written.  No atomics of its own, nothing synchronises, nothing is read back.
+ *   workspace: pointops_radius_outlier_workspace_bytes(N, P); a short or null one is POINTOPS_EWORKSPACE with nothing
+ *   written.  0 <= N < 65536 (a bigger batch goes in slices), 0 <= P < 2^30, 1 <= D <= 3, radius finite and > 0,
+ *   min_neighbors >= 0: anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing; P == 0
+ *   writes num_kept = 0.
+ *
+ * STATISTICAL FILTER (pointops_statistical_outlier): keep the rows whose mean distance to their nearest neighbours
+ * is not far above the cloud's.
+ *   dists (N,P,K1) fp32: the SQUARED distances of knn_points of the cloud against itself with K = K1, ascending, the
+ *   row's own zero distance among them; K1 = nb_neighbors + 1.  lengths (N,) or NULL (= P; clamped into [0,P]).
+ *   Per cloud n with len = its length and cnt = min(K1, len):
+ *   1. ROW MEAN, for every row i < len.  cnt >= 2:  m_i = fl32( (sum over k < cnt of sqrt((double)dists[n,i,k]))
+ *      / (double)(cnt - 1) ), the sum in fp64 in ascending k, starting from +0.0.  The row's own distance adds 0: this
+ *      is PCL's mean over the nb_neighbors nearest OTHER points (Open3D's at nb_neighbors = K1 times K1 / (K1 - 1):
+ *      the same mask).  cnt < 2: m_i = 0.  A row is FINITE when m_i is; the others take no part in step 2 and get
+ *      mask 0.  mean_distance[n,i] = m_i; 0 on rows at or past the length.
+ *   2. CLOUD STATISTICS in fp64, two passes.  n_f = the number of finite rows.  S1 = SUM(m_i), mean = S1 / n_f (0 when
+ *      n_f == 0); S2 = SUM((m_i - mean) * (m_i - mean)), std = sqrt(S2 / (n_f - 1)) (0 when n_f < 2).  Both SUMs are
+ *      taken over the P rows of the cloud, a row that is not finite or at or past the length entering as +0.0, by one
+ *      tree whose shape depends on the row index alone -- not on N, the launch, the device or a debug knob:
+ *        - row i belongs to chunk i / 4096 and, within it, to lane (i % 4096) % 256;
+ *        - every lane adds its rows of the chunk one after the other, in ascending order, to +0.0 (16 additions);
+ *        - the 256 lane sums s[0 .. 256) of a chunk are folded by s[t] = s[t] + s[t + h] for t < h, with
+ *          h = 128, 64, ..., 1 in turn: the chunk's sum is s[0];
+ *        - the chunk sums are added one after the other, in ascending chunk order, to +0.0.
+ *   3. THRESHOLD AND MASK.  threshold[n] = fl32(mean + (double)std_ratio * std); mask[n,i] = 1 iff row i is finite and
+ *      m_i <= threshold[n], an fp32 comparison: a lattice whose m_i are all equal keeps every row.
+ *   4. index, num_kept: the COMPACTION of mask.
+ *   Outputs: mean_distance (N,P) fp32, stats (N,3) fp64 = (mean, std, n_f), threshold (N,) fp32, mask (N,P) one byte
+ *   0/1 per row, index (N,P) int64, num_kept (N,) int64.  Every output is fully written.  No atomics, nothing
+ *   synchronises, nothing is read back: two calls are byte-equal, a cloud gives the same rows alone and in a batch.
+ *   The row formula, the finite test, std and threshold are csrc/filter_stats.h, host and device code.
+ *   workspace: pointops_statistical_outlier_workspace_bytes(N, P); a short or null one is POINTOPS_EWORKSPACE with
+ *   nothing written.  0 <= N < 65536 (a bigger batch goes in slices), 0 <= P <= 2^24, 2 <= K1 <= 128, std_ratio finite
+ *   and >= 0: anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing; P == 0 writes stats =
+ *   (0, 0, 0), threshold = 0 and num_kept = 0.
+ */
+int pointops_mask_compact(const uint8_t* mask, int64_t N, int64_t P, int64_t* index, int64_t* num_kept, void* stream);
+size_t pointops_radius_outlier_workspace_bytes(int64_t N, int64_t P);
+int pointops_radius_outlier(const float* points, const int64_t* lengths, int64_t N, int64_t P, int64_t D, float radius,
+                            int64_t min_neighbors, uint8_t* mask, int32_t* counts, int64_t* index, int64_t* num_kept,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t pointops_statistical_outlier_workspace_bytes(int64_t N, int64_t P);
+int pointops_statistical_outlier(const float* dists, const int64_t* lengths, int64_t N, int64_t P, int64_t K1,
+                                 float std_ratio, float* mean_distance, double* stats, float* threshold, uint8_t* mask,
+                                 int64_t* index, int64_t* num_kept, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,12 @@ _SIGNATURES = {
     "pointops_voxel_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pointops_voxel_downsample": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _sz, _vp]),
+    "pointops_mask_compact": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "pointops_radius_outlier_workspace_bytes": (_sz, [_i64, _i64]),
+    "pointops_radius_outlier": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pointops_statistical_outlier_workspace_bytes": (_sz, [_i64, _i64]),
+    "pointops_statistical_outlier": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                            _vp]),
     "pointops_plane_chunk": (_i64, []),
     "pointops_plane_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pointops_segment_plane": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _int, _f32, _f32, _f32,

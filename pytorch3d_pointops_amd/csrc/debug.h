@@ -31,6 +31,7 @@
 //   plane_hpl=1|2      segment_plane scoring: hypotheses per lane (default: 2 above 256 hypotheses)
 //   cluster_grid=0|1   cluster_dbscan: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   iss_grid=0|1       iss_keypoints: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
+//   filter_grid=0|1    remove_radius_outlier: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   voxel_long=0|1     voxel_downsample: every voxel summed by one lane / by one wave (default: a wave above 16 members)
 #pragma once
 

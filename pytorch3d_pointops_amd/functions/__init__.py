@@ -3,6 +3,8 @@
 from .. import ops as _ops  # noqa: F401  registers torch.ops.pointops_amd.* (torch.compile traces through them)
 from .ball_query import ball_query
 from .cluster import DBSCANClusters, cluster_dbscan, euclidean_clusters
+from .filters import (RadiusOutliers, SelectedRows, StatisticalOutliers, mask_to_index, remove_radius_outlier,
+                      remove_statistical_outlier, select_rows)
 from .fpfh import fpfh_features, mutual_nearest_neighbors, point_pair_features
 from .iss import ISSKeypoints, cloud_resolution, iss_keypoints, keypoints_to_padded
 from .knn import knn_gather, knn_points

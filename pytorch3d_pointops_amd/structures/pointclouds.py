@@ -233,6 +233,22 @@ class Pointclouds:
 
         return iss_keypoints(self, **kwargs)
 
+    def remove_radius_outlier(self, **kwargs):
+        """(a new Pointclouds of the points with at least `min_neighbors` others within `radius`, every feature carried
+        over; the RadiusOutliers of functions.remove_radius_outlier, same keywords)."""
+        from ..functions.filters import filtered_pointclouds, remove_radius_outlier
+
+        r = remove_radius_outlier(self, **kwargs)
+        return filtered_pointclouds(self, r), r
+
+    def remove_statistical_outlier(self, **kwargs):
+        """(a new Pointclouds without the points whose mean neighbour distance is far above their cloud's, every feature
+        carried over; the StatisticalOutliers of functions.remove_statistical_outlier, same keywords)."""
+        from ..functions.filters import filtered_pointclouds, remove_statistical_outlier
+
+        r = remove_statistical_outlier(self, **kwargs)
+        return filtered_pointclouds(self, r), r
+
     def segment_plane(self, **kwargs):
         """PlaneSegmentation(planes (N, 4), inliers (N, max P_n) bool, num_inliers (N,), rmse (N,), best (N,), ...) of
         every cloud (functions.segment_plane, same keywords): the dominant plane, padding rows never inliers."""
