@@ -379,6 +379,79 @@ int pointops_icp_iteration(const float* X_init, float* Xt, const float* Y, const
                            void* stream);
 
 /*
+ * REGISTRATION.  One step of registration_icp -- trimmed point-to-plane or point-to-point ICP (Open3D's
+ * registration_icp with a mandatory max_correspondence_distance; PCL's IterativeClosestPoint with
+ * setMaxCorrespondenceDistance) -- device half of functions/registration.py.  The semantics are this library's own.
+ * float32, three dimensions, rigid motion only; the row-vector convention x -> x R + T throughout.
+ *   X_init (N,P1,3), Y (N,P2,3), target_normals (N,P2,3) fp32 (NULL allowed for point to point; used as given, never
+ *   renormalised), lengths_x, lengths_y (N,) (clamped into [0,P]); 1 <= N < 65536, P1, P2 >= 1.
+ *   R_init (N,3,3), T_init (N,3) fp32 or NULL (the identity): read only when `first` != 0.
+ * Per cloud the run keeps, in buffers the caller owns and passes to every step:
+ *   state (N,16) fp64: the accumulated transform R (9, row-major), T (3), prev_fitness, prev_rmse, 2 spare words;
+ *   status (N,) int32: 2 = running, 0 = frozen, converged, 1 = frozen, degenerate;  iterations (N,) int32: updates
+ *   applied;  Xt (N,P1,3) fp32: the transformed cloud, the queries of the search.
+ * `first` != 0 (step i = 0) initialises all of them (they may be uninitialised on entry): state from R_init / T_init,
+ * status 2, iterations 0, Xt = X_init R_init + T_init in the fp32 arithmetic of step 7.
+ * Step i, for every cloud with status 2 (a frozen cloud leaves everything as it is: see step 7):
+ *   1. Search: idx (N,P1) int64, dists (N,P1) fp32 = the K=1, L2 pointops_knn_points_idx_reuse of Xt in Y on
+ *      `knn_workspace` (pointops_knn_workspace_bytes(N,P1,P2,3,1,search_version) bytes).  search_version is what
+ *      pointops_registration_search_version() returned when the run began (-1, the search's own choice of kernel family
+ *      by shape, unless a debug knob forces the grid; it never changes results): a run asks once and passes the same
+ *      value to every step, since the workspace built by step 0 belongs to one family.  reuse: 0 = build the search structure,
+ *      1 = the caller vouches that Y, lengths_y and the shape are those of the previous call into knn_workspace.
+ *      d2 = dists[n,r], j = idx[n,r].  (The search runs for the whole batch; a frozen cloud's rows come out unchanged.)
+ *   2. Inliers: row r is an inlier iff r < lengths_x[n], lengths_y[n] > 0 and d2 < fl32(max_correspondence_distance *
+ *      max_correspondence_distance) -- ball_query's rule.  correspondences[n,r] = j for an inlier, else -1.
+ *   3. Evaluation: c = the number of inliers, fitness = fl32(c / max(lengths_x[n], 1)) and
+ *      inlier_rmse = fl32(sqrt(sum d2 / max(c, 1))) with the sum and the quotients in fp64: they describe the transform
+ *      in effect at the search.  num_correspondences[n] = c.
+ *   4. If i > 0 and |fitness - prev_fitness| < relative_fitness and |inlier_rmse - prev_rmse| < relative_rmse (fp64
+ *      differences of the fp32 values; Open3D's absolute differences despite the names): status = 0.  In every case
+ *      prev_fitness = fitness and prev_rmse = inlier_rmse afterwards.
+ *   5. Otherwise, when `update` != 0:
+ *      estimation 1, point to plane: with the pivot c0 = Xt[n,0] and, per inlier, p = Xt - c0, q = Y[j],
+ *        n = target_normals[j], rho = (Xt - q).n, J = [p x n, n] (all fp64 from the fp32 values):  A = sum J^T J (the 21
+ *        entries of its upper triangle, row by row), b = -sum J rho.  A x = b by an fp64 Cholesky, x = (alpha, beta,
+ *        gamma, t);  Rd = (Rz(gamma) Ry(beta) Rx(alpha))^T, built from the sines and cosines, not linearised;
+ *        R <- R Rd and T <- (T - c0) Rd + c0 + t.
+ *      estimation 0, point to point: (R, T) <- pointops_points_alignment's solve of the ORIGINAL rows X_init onto Y[j]
+ *        with weight 1 on inliers and 0 elsewhere (the 24 moments about the pivots X_init[n,0], Y[n,0]; eps 1e-9, no
+ *        scale, no reflection).
+ *      iterations += 1.
+ *   6. Instead of 5, status = 1 and the transform stays as it is when c < 6 (point to plane) or c < 3 (point to
+ *      point), or when a Cholesky pivot -- the diagonal entry of row j after the eliminations of the rows before it --
+ *      is not greater than kIcpDegeneratePivot = 1e-10 times the ORIGINAL diagonal entry of that row.  A definition,
+ *      not a measurement; one plane as the target (rank 3) trips it.
+ *   7. R (N,3,3), T (N,3) = fl32 of the accumulated transform, fitness (N,), inlier_rmse (N,): this step's history
+ *      entry, written for EVERY cloud (a frozen one repeats its last entry).  With `update` != 0, every cloud that step
+ *      5 moved gets Xt = X_init R + T from those fp32 values, v = ((x0 R[0][k] + x1 R[1][k]) + x2 R[2][k]) + T[k],
+ *      unfused; rows >= lengths_x[n] are zero.
+ *   all_frozen[0] = 1 when no cloud has status 2 after the step, else 0.
+ *   moments (N,35) fp64 or NULL, for tests: the reduced sums of the step -- point to plane: A (21), b (6), c, sum d2;
+ *   point to point: the 24 moments of pointops_points_alignment, three zeros, c, sum d2 -- and, in words 29..34, the x =
+ *   (alpha, beta, gamma, t) that step 5's Cholesky solved (zeros for point to point and wherever step 5 did not move
+ *   the cloud).  All 35 words are zero for a frozen cloud.
+ * `update` == 0 is the evaluate-only step (1-4 and 7).  Since a frozen cloud does nothing, enqueueing more steps than
+ * a run needs is legal and changes no byte: a host loop may read all_frozen as rarely as it likes, or never.
+ * All sums are fp64 in an order fixed by the row index and the launch shape (a function of P1 alone): two calls are
+ * byte-equal, and a cloud gives the same bytes alone and inside any batch of the same padded widths.  No
+ * floating-point atomics.  workspace: pointops_registration_workspace_bytes(N, P1).  A short or null workspace of
+ * either kind is POINTOPS_EWORKSPACE and nothing is launched.  Nothing synchronises.
+ */
+int pointops_registration_search_version(void);
+size_t pointops_registration_workspace_bytes(int64_t N, int64_t P1);
+int pointops_registration_step(const float* X_init, const float* Y, const float* target_normals,
+                               const int64_t* lengths_x, const int64_t* lengths_y, const float* R_init,
+                               const float* T_init, int64_t N, int64_t P1, int64_t P2,
+                               float max_correspondence_distance, double relative_fitness, double relative_rmse,
+                               int estimation, int update, int first, int reuse, int search_version, float* Xt,
+                               double* state, int32_t* status, int32_t* iterations, int64_t* idx, float* dists,
+                               int64_t* correspondences, int64_t* num_correspondences, float* R, float* T,
+                               float* fitness, float* inlier_rmse, int32_t* all_frozen, double* moments,
+                               void* knn_workspace, size_t knn_workspace_bytes, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/*
  * Fast Point Feature Histograms (Rusu et al. 2009; 33 bins per point, three groups of 11) and the point-pair features
  * under them, in two fused passes over a neighbour table -- device half of functions/fpfh.py.  The semantics are this
  * library's own; all arithmetic is unfused fp32 in the order written.

@@ -73,6 +73,11 @@ _SIGNATURES = {
     "pointops_icp_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pointops_icp_iteration": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _f32,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "pointops_registration_search_version": (_int, []),
+    "pointops_registration_workspace_bytes": (_sz, [_i64, _i64]),
+    "pointops_registration_step": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f64, _f64, _int,
+                                          _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "pointops_spfh": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "pointops_fpfh": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "pointops_ransac_chunk": (_i64, []),

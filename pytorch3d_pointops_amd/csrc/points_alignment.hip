@@ -24,57 +24,11 @@
 // grid over the unmodified target cloud is built once per ICP run) with 1-3.  The backward of the alignment is the
 // elementwise alignment_backward_kernel: the gradient of the moments (from the host's float64 autograd of the N tiny
 // solves) pushed to X, Y and the weights.
+#include "block_sum.h"
 #include "common.h"
 #include "small_solvers.h"
 
 namespace pointops {
-
-constexpr int kPaBlock = 256;          // threads per block of the point passes
-constexpr int kPaWaves = kPaBlock / kWave;
-constexpr int kPaRowsPerThread = 8;    // rows per thread before a cloud gets another block
-constexpr int kPaMaxBlocks = 32;       // partials per cloud (the solve sums them one after the other)
-
-inline int pa_blocks(int64_t P) {
-  const int64_t nb = ceil_div(P, (int64_t)kPaBlock * kPaRowsPerThread);
-  return (int)(nb < 1 ? 1 : (nb > kPaMaxBlocks ? kPaMaxBlocks : nb));
-}
-
-// v + (v of the lane DPP control CTRL names); lanes outside the rows of ROWS add 0
-template <int CTRL, int ROWS>
-__device__ __forceinline__ double pa_dpp_add(double v) {
-  const int hi = __double2hiint(v), lo = __double2loint(v);
-  const int ohi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROWS, 0xf, false);
-  const int olo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROWS, 0xf, false);
-  return v + __hiloint2double(ohi, olo);
-}
-// sum over the wave (all 64 lanes must be active); the result is valid in lane 63
-__device__ __forceinline__ double pa_wave_sum_lane63(double v) {
-  v = pa_dpp_add<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v = pa_dpp_add<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-  v = pa_dpp_add<0x124, 0xf>(v);  // row_ror 4
-  v = pa_dpp_add<0x128, 0xf>(v);  // row_ror 8
-  v = pa_dpp_add<0x142, 0xa>(v);  // row_bcast15 into rows 1, 3
-  v = pa_dpp_add<0x143, 0xc>(v);  // row_bcast31 into rows 2, 3
-  return v;
-}
-
-// Block sum of M per-thread fp64 values: out[m] (m < M) written by thread m.  Every thread of the block calls it.
-template <int M>
-__device__ __forceinline__ void pa_block_sum(const double (&acc)[M], double (*s_part)[M], double* __restrict__ out) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    const double v = pa_wave_sum_lane63(acc[m]);
-    if (lane == kWave - 1) s_part[wave][m] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < M) {
-    double v = s_part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kPaWaves; ++w) v += s_part[w][threadIdx.x];
-    out[threadIdx.x] = v;
-  }
-}
 
 // The pivots of cloud n: row 0 of X and of Y (zero for a cloud without rows).
 template <int D>

@@ -14,6 +14,7 @@ from .points_alignment import (ICPSolution, SimilarityTransform, corresponding_p
 from .plane import PlaneSegmentation, PlaneSet, segment_plane, segment_planes
 from .points_normals import estimate_pointcloud_local_coord_frames, estimate_pointcloud_normals
 from .ransac import RansacSolution, ransac_alignment
+from .registration import RegistrationHistory, RegistrationResult, evaluate_registration, registration_icp
 from .sample_farthest_points import sample_farthest_points
 from .utils import convert_pointclouds_to_tensor, get_point_covariances, masked_gather, wmean
 from .voxel import VoxelDownsample, voxel_downsample, voxels_to_padded

@@ -256,6 +256,21 @@ class Pointclouds:
 
         return segment_plane(self, **kwargs)
 
+    def registration_icp(self, target, max_correspondence_distance: float, **kwargs):
+        """RegistrationResult(R, T, fitness, inlier_rmse, ..., Xt: this batch moved onto `target`) of the trimmed ICP of
+        every cloud onto the cloud of `target` with the same index (functions.registration_icp, same keywords):
+        point-to-plane by default, with the target's feature "normals"."""
+        from ..functions.registration import registration_icp
+
+        return registration_icp(self, target, max_correspondence_distance, **kwargs)
+
+    def evaluate_registration(self, target, max_correspondence_distance: float, transform=None):
+        """The fitness, inlier rmse and correspondences of this batch under `transform` against `target`
+        (functions.evaluate_registration)."""
+        from ..functions.registration import evaluate_registration
+
+        return evaluate_registration(self, target, max_correspondence_distance, transform)
+
     def voxel_downsample(self, voxel_size: float, **kwargs) -> "Pointclouds":
         """A new batch with one point per occupied voxel of every cloud -- the centroid of the voxel's points -- and
         every feature averaged over the same points (functions.voxel_downsample, same keywords, plus `check` of
