@@ -64,6 +64,23 @@ int pointops_knn_points_idx(const float* p1, const float* p2, const int64_t* len
                             void* stream);
 
 /*
+ * Read-only view of the dispatch (tests, tools): the kernel family a pointops_knn_points_idx call of this shape and
+ * `version` takes and the number of p2 slices it scans (1 = none; > 1: partial lists merged by a second launch),
+ * debug knobs included.  Launches nothing, needs no device, changes no choice.  HOST pointers; returns POINTOPS_OK.
+ *   *family: 0 nothing to search (N or P1 = 0), 1 grid-pruned search, 2 LDS-transposed queries (any D; register
+ *            lists up to K = 32, 64-slot register lists to 64, LDS lists above), 3 plain generic kernel,
+ *            4 one wave per query, 5 register scan, one lane per query.
+ */
+#define POINTOPS_KNN_FAMILY_NONE 0
+#define POINTOPS_KNN_FAMILY_GRID 1
+#define POINTOPS_KNN_FAMILY_WIDE 2
+#define POINTOPS_KNN_FAMILY_GENERIC 3
+#define POINTOPS_KNN_FAMILY_SMALL 4
+#define POINTOPS_KNN_FAMILY_SCAN 5
+int pointops_knn_plan(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K, int version, int* family,
+                      int* splits);
+
+/*
  * The same operator REUSING the cell grid a previous call left in `workspace` (the grid-pruned family only:
  * pointops_knn_uses_grid(...) != 0 for the shape; other families ignore `reuse`).  The reference has no counterpart --
  * its operator (csrc/knn/knn.h:59-66) is stateless -- so this is an extension for callers that query the same target

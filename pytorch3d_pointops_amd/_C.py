@@ -37,6 +37,7 @@ _SIGNATURES = {
     "pointops_knn_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _int]),
     "pointops_knn_points_idx": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _i64, _int,
                                        _vp, _vp, _vp, _sz, _vp]),
+    "pointops_knn_plan": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _vp, _vp]),
     "pointops_knn_uses_grid": (_int, [_i64, _i64, _i64, _i64, _i64, _int]),
     "pointops_knn_points_idx_reuse": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _i64, _int,
                                              _vp, _vp, _vp, _sz, _int, _vp]),
@@ -241,9 +242,12 @@ def _bind(name, argtypes):
     return scope[name]
 
 
+# entries that return a code and end in a pointer which is a HOST output, not a stream: they launch nothing
+_HOST_QUERIES = ("pointops_knn_plan",)
+
 # _call.<entry without "pointops_">(what, dev, *args) for every entry that launches (returns a code, takes a stream)
 _call = types.SimpleNamespace(**{name[len("pointops_"):]: _bind(name, args) for name, (res, args) in _SIGNATURES.items()
-                                 if res is _int and args and args[-1] is _vp})
+                                 if res is _int and args and args[-1] is _vp and name not in _HOST_QUERIES})
 
 
 # The three names every device buffer that a native call writes comes through -- outputs (_out, _out_like) and scratch
@@ -399,6 +403,18 @@ def knn_grid_stats(p1, p2, lengths1, lengths2, norm: int, K: int):
     point / query sort."""
     return _grid_diagnostics(p1, p2, lengths1, lengths2, norm, K, lambda N: (N, 14), _call.knn_grid_stats,
                              "knn_grid_stats")
+
+
+KNN_FAMILIES = ("none", "grid", "wide", "generic", "small", "scan")  # POINTOPS_KNN_FAMILY_* of the header, in order
+
+
+def knn_plan(N: int, P1: int, P2: int, D: int, K: int, version: int = -1):
+    """(family name, p2 slices) of the knn_points_idx call of this shape: the dispatch's own answer, debug knobs
+    included (pointops_knn_plan).  Host only: nothing is launched."""
+    family, splits = ctypes.c_int(-1), ctypes.c_int(-1)
+    _check(_lib.pointops_knn_plan(int(N), int(P1), int(P2), int(D), int(K), int(version), ctypes.byref(family),
+                                  ctypes.byref(splits)), "knn_plan")
+    return KNN_FAMILIES[family.value], splits.value
 
 
 def knn_check_version(version: int, D: int, K: int) -> bool:

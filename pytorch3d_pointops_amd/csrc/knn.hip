@@ -279,6 +279,21 @@ size_t pointops_knn_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D
   return knn_plan(N, P1, P2, D, K, version).workspace_bytes;
 }
 
+static_assert((int)KnnFamily::kNone == POINTOPS_KNN_FAMILY_NONE && (int)KnnFamily::kGrid == POINTOPS_KNN_FAMILY_GRID &&
+                  (int)KnnFamily::kWide == POINTOPS_KNN_FAMILY_WIDE &&
+                  (int)KnnFamily::kGeneric == POINTOPS_KNN_FAMILY_GENERIC &&
+                  (int)KnnFamily::kSmall == POINTOPS_KNN_FAMILY_SMALL && (int)KnnFamily::kScan == POINTOPS_KNN_FAMILY_SCAN,
+              "the header's family numbers are KnnFamily's");
+
+int pointops_knn_plan(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K, int version, int* family,
+                      int* splits) {
+  POINTOPS_REQUIRE(family && splits, "knn_plan: null pointer");
+  const KnnPlan plan = knn_plan(N, P1, P2, D, K, version);
+  *family = (int)plan.family;
+  *splits = plan.splits;
+  return POINTOPS_OK;
+}
+
 int pointops_knn_points_idx(const float* p1, const float* p2, const int64_t* lengths1,
                             const int64_t* lengths2, int64_t N, int64_t P1, int64_t P2, int64_t D,
                             int norm, int64_t K, int version, int64_t* idxs, float* dists,

@@ -263,7 +263,7 @@ class Contract:
             def __getattr__(self, name):
                 fn = getattr(lib, name)
                 res, argtypes = signatures.get(name, (None, []))
-                if res is not ctypes.c_int or not argtypes or argtypes[-1] is not vp:
+                if res is not ctypes.c_int or not argtypes or argtypes[-1] is not vp or name == "pointops_knn_plan":
                     return fn  # sizers and queries: nothing is launched
                 ws_at = [i for i in range(len(argtypes) - 1) if argtypes[i] is vp and argtypes[i + 1] is sz]
 
