@@ -5,9 +5,8 @@
 // points numbered by their smallest member, a border point takes the smallest label among its core neighbours.
 //
 // A fixed sequence of launches, stream-ordered, nothing read back; the kernel boundary is the only synchronisation:
-//   lengths   the cloud lengths clamped into [0, P] (a null `lengths` = P), for grid_build and every pass
-//   grid      grid_build with same = true, h_min = 1.001 eps, refine = -1 (the KNN-style workspace): the cloud sorted
-//             by cells at least eps wide -- for clouds of kClusterGridMinPoints points and more
+//   prepare   radius_walk_prepare with cell_radius = eps: the lengths clamped into [0, P], and for clouds of 512 points
+//             and more the cloud sorted by cells at least eps wide
 //   count     one lane per point: neighbours counted up to min_points -> core_mask; parent[i] = i
 //   union     core lanes walk again: uf_union(i, j) for every core neighbour j < i (cluster_union.h: lock-free,
 //             relaxed agent-scope atomics only, the root of a component = its smallest index)
@@ -15,69 +14,62 @@
 //             the roots it reads are final only once every hook of the union launch has been made.
 //   scan      one workgroup per cloud: the roots (label == own index) ranked in index order -> rank[], num_clusters
 //   relabel   label = rank[root]
-// A WALK is radius_walk.h's (shared with iss.hip): the 3x3x3 cube around the lane's cell under ball query's certificate,
+// A WALK is radius_walk.h's: the 3x3x3 cube around the lane's cell under ball query's certificate,
 // else the raw cloud by all pairs with the same comparison, so which path a lane takes depends on the input alone and
 // never changes a result.  POINTOPS_DEBUG=cluster_grid=0 sends every cloud by all pairs.
 #include <limits.h>
 
 #include "cluster_union.h"
-#include "debug.h"
-#include "grid.h"
 #include "radius_walk.h"
 #include "wave.h"
 
 namespace pointops {
 
 constexpr int kClScanBlock = 1024;
-constexpr float kClusterCellTarget = 2.0f;    // density floor of the cell size (ball query's); eps usually decides
-constexpr int kClusterGridMinPoints = 512;    // smaller clouds: all pairs (the build's fixed passes cost more)
 
 template <int D>
-__global__ __launch_bounds__(kClBlock) void cluster_count_kernel(ClusterView v, int min_points,
-                                                               uint8_t* __restrict__ core_mask,
-                                                               int* __restrict__ parent) {
-  GridCloud g = {};
-  const ClusterItem it = cluster_item(v, g);
+__global__ __launch_bounds__(kWalkBlock) void cluster_count_kernel(WalkView v, int min_points,
+                                                                   uint8_t* __restrict__ core_mask,
+                                                                   int* __restrict__ parent) {
+  const WalkItem it = walk_item(v);
   if (it.t >= v.P) return;
   if (it.t >= it.len) {
     core_mask[(int64_t)it.n * v.P + it.t] = 0;  // padding rows
     return;
   }
-  const ClusterLane<D> L = cluster_lane<D>(v, g, it.grid, it.n, it.t);
+  const WalkLane<D> L = walk_lane<D>(v, it);
   int cnt = 0;
-  cluster_walk<D>(v, g, L, it.n, it.len, [&](int) { return ++cnt < min_points; });
+  radius_walk<D>(v, it, L, [&](int) { return ++cnt < min_points; });
   core_mask[(int64_t)it.n * v.P + L.i] = cnt >= min_points ? 1 : 0;
   parent[(int64_t)it.n * v.P + L.i] = L.i;
 }
 
 template <int D>
-__global__ __launch_bounds__(kClBlock) void cluster_union_kernel(ClusterView v, const uint8_t* __restrict__ core_mask,
-                                                               int* parent) {
-  GridCloud g = {};
-  const ClusterItem it = cluster_item(v, g);
+__global__ __launch_bounds__(kWalkBlock) void cluster_union_kernel(WalkView v, const uint8_t* __restrict__ core_mask,
+                                                                   int* parent) {
+  const WalkItem it = walk_item(v);
   if (it.t >= it.len) return;
-  const ClusterLane<D> L = cluster_lane<D>(v, g, it.grid, it.n, it.t);
+  const WalkLane<D> L = walk_lane<D>(v, it);
   const uint8_t* __restrict__ core = core_mask + (int64_t)it.n * v.P;
   if (!core[L.i]) return;
   int* const par = parent + (int64_t)it.n * v.P;
   int up = L.i;  // an ancestor-or-self of this point: the unions start from it, not from the point every time
-  cluster_walk<D>(v, g, L, it.n, it.len, [&](int j) {
+  radius_walk<D>(v, it, L, [&](int j) {
     if (j < L.i && core[j]) up = uf_union(par, up, j);  // (every edge once: from its larger end)
     return true;
   });
 }
 
 template <int D>
-__global__ __launch_bounds__(kClBlock) void cluster_flatten_kernel(ClusterView v, const uint8_t* __restrict__ core_mask,
-                                                                 int* parent, int64_t* __restrict__ labels) {
-  GridCloud g = {};
-  const ClusterItem it = cluster_item(v, g);
+__global__ __launch_bounds__(kWalkBlock) void cluster_flatten_kernel(WalkView v, const uint8_t* __restrict__ core_mask,
+                                                                     int* parent, int64_t* __restrict__ labels) {
+  const WalkItem it = walk_item(v);
   if (it.t >= v.P) return;
   if (it.t >= it.len) {
     labels[(int64_t)it.n * v.P + it.t] = -1;  // padding rows
     return;
   }
-  const ClusterLane<D> L = cluster_lane<D>(v, g, it.grid, it.n, it.t);
+  const WalkLane<D> L = walk_lane<D>(v, it);
   const uint8_t* __restrict__ core = core_mask + (int64_t)it.n * v.P;
   int* const par = parent + (int64_t)it.n * v.P;
   int root;
@@ -85,7 +77,7 @@ __global__ __launch_bounds__(kClBlock) void cluster_flatten_kernel(ClusterView v
     root = uf_find(par, L.i);
   } else {
     root = INT_MAX;  // the smallest root = the smallest label: clusters are numbered by their smallest member
-    cluster_walk<D>(v, g, L, it.n, it.len, [&](int j) {
+    radius_walk<D>(v, it, L, [&](int j) {
       if (core[j]) root = min(root, uf_find(par, j));
       return true;
     });
@@ -115,9 +107,9 @@ __global__ __launch_bounds__(kClScanBlock) void cluster_scan_kernel(const int64_
   if (tid == 0) num_clusters[n] = base;
 }
 
-__global__ __launch_bounds__(kClBlock) void cluster_relabel_kernel(const int64_t* __restrict__ len, int P,
-                                                                 const int* __restrict__ rank, int64_t* labels) {
-  const int n = blockIdx.y, i = blockIdx.x * kClBlock + threadIdx.x;
+__global__ __launch_bounds__(kWalkBlock) void cluster_relabel_kernel(const int64_t* __restrict__ len, int P,
+                                                                     const int* __restrict__ rank, int64_t* labels) {
+  const int n = blockIdx.y, i = blockIdx.x * kWalkBlock + threadIdx.x;
   if (i >= (int)len[n]) return;
   const int64_t root = labels[(int64_t)n * P + i];
   if (root >= 0) labels[(int64_t)n * P + i] = rank[(int64_t)n * P + root];
@@ -128,28 +120,19 @@ static bool cluster_shape_ok(int64_t N, int64_t P, int64_t D) {
   return N >= 0 && N < 65536 && P >= 0 && P < (1LL << 30) && D >= 1 && D <= 3;
 }
 
-// whether the call builds grids (the per-cloud decision is grid_build's, on the device)
-static bool cluster_uses_grid(int64_t N, int64_t P) {
-  const long force = debug_knob("cluster_grid", -1);  // 0 = never, 1 = whenever the shape allows (tests)
-  if (force == 0 || N <= 0 || P <= 0 || P > knn_grid_max_points()) return false;
-  return force == 1 || P >= kClusterGridMinPoints;
-}
-
 struct ClusterLayout {
-  int64_t* len;  // (N,)
+  WalkLayout walk;
   int* parent;   // (N, P)
   int* rank;     // (N, P)
-  char* grid;    // grid_carve's
   size_t bytes;
 };
 
-static ClusterLayout cluster_layout(void* ws, int64_t N, int64_t P, bool grid) {
+static ClusterLayout cluster_layout(void* ws, int64_t N, int64_t P) {
   Carver c(ws);
   ClusterLayout l;
-  l.len = (int64_t*)c.take(sizeof(int64_t) * (size_t)N);
+  l.walk = radius_walk_carve(c, "cluster_grid", N, P);
   l.parent = (int*)c.take(sizeof(int) * (size_t)N * (size_t)P);
   l.rank = (int*)c.take(sizeof(int) * (size_t)N * (size_t)P);
-  l.grid = c.take(grid ? grid_carve(nullptr, nullptr, N, P, P, kClusterCellTarget) : 0);
   l.bytes = c.off;
   return l;
 }
@@ -160,7 +143,7 @@ using namespace pointops;
 
 extern "C" size_t pointops_cluster_workspace_bytes(int64_t N, int64_t P) {
   if (!cluster_shape_ok(N, P, 3) || N == 0) return 0;
-  return cluster_layout(nullptr, N, P, cluster_uses_grid(N, P)).bytes;
+  return cluster_layout(nullptr, N, P).bytes;
 }
 
 extern "C" int pointops_cluster_dbscan(const float* points, const int64_t* lengths, int64_t N, int64_t P, int64_t D,
@@ -170,53 +153,29 @@ extern "C" int pointops_cluster_dbscan(const float* points, const int64_t* lengt
   POINTOPS_REQUIRE(eps > 0.0f && eps <= FLT_MAX && min_points >= 1,
                    "cluster_dbscan: need a finite eps > 0 and min_points >= 1");
   if (N == 0) return POINTOPS_OK;
-  const bool grid = cluster_uses_grid(N, P);
-  const ClusterLayout l = cluster_layout(workspace, N, P, grid);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("cluster_dbscan: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  const ClusterLayout l = cluster_layout(workspace, N, P);
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "cluster_dbscan: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(cluster_lengths_kernel, dim3((unsigned)ceil_div(N, kClBlock)), dim3(kClBlock), 0, stream, lengths,
-                     (int)N, (int)P, l.len);
-  ClusterView v{};
-  v.points = points;
-  v.len = l.len;
-  v.P = (int)P;
+  WalkView v;
+  const int rc = radius_walk_prepare(l.walk, points, lengths, N, P, D, eps, stream, &v);
+  if (rc != POINTOPS_OK) return rc;
   v.r2 = eps * eps;  // fp32 product, as ball query's radius2
-  if (grid) {
-    GridWs ws;
-    grid_carve(&ws, l.grid, N, P, P, kClusterCellTarget);
-    // K = 0: the build's padding of search rows has nothing to write
-    const KnnArgs a = make_knn_args(points, points, l.len, l.len, N, P, P, D, 0, 0, nullptr, nullptr, stream);
-    GridBuild b{};
-    b.c_target = kClusterCellTarget;
-    b.h_min = eps * 1.001f;
-    b.same = true;
-    b.refine = -1;
-    const int rc = grid_build(a, ws, b);
-    if (rc != POINTOPS_OK) return rc;
-    v.clouds = ws.cloud;
-    v.edges = ws.edges;
-    v.cell_start = ws.cell_start;
-    v.sorted = ws.sorted;
-    v.cell_cap = ws.cell_cap;
-  }
   const int minp = (int)(min_points > INT_MAX ? INT_MAX : min_points);
   if (P > 0) {
-    const dim3 pgrid((unsigned)ceil_div(P, kClBlock), (unsigned)N);
+    const dim3 pgrid((unsigned)ceil_div(P, kWalkBlock), (unsigned)N);
     with_exact<3>(Ints<1, 2, 3>{}, (int)D, [&](auto DT) {
-      hipLaunchKernelGGL((cluster_count_kernel<DT>), pgrid, dim3(kClBlock), 0, stream, v, minp, core_mask, l.parent);
-      hipLaunchKernelGGL((cluster_union_kernel<DT>), pgrid, dim3(kClBlock), 0, stream, v, (const uint8_t*)core_mask,
+      hipLaunchKernelGGL((cluster_count_kernel<DT>), pgrid, dim3(kWalkBlock), 0, stream, v, minp, core_mask, l.parent);
+      hipLaunchKernelGGL((cluster_union_kernel<DT>), pgrid, dim3(kWalkBlock), 0, stream, v, (const uint8_t*)core_mask,
                          l.parent);
-      hipLaunchKernelGGL((cluster_flatten_kernel<DT>), pgrid, dim3(kClBlock), 0, stream, v, (const uint8_t*)core_mask,
+      hipLaunchKernelGGL((cluster_flatten_kernel<DT>), pgrid, dim3(kWalkBlock), 0, stream, v, (const uint8_t*)core_mask,
                          l.parent, labels);
     });
   }
-  hipLaunchKernelGGL(cluster_scan_kernel, dim3((unsigned)N), dim3(kClScanBlock), 0, stream, (const int64_t*)l.len, (int)P,
+  hipLaunchKernelGGL(cluster_scan_kernel, dim3((unsigned)N), dim3(kClScanBlock), 0, stream, v.len, (int)P,
                      (const int64_t*)labels, l.rank, num_clusters);
   if (P > 0)
-    hipLaunchKernelGGL(cluster_relabel_kernel, dim3((unsigned)ceil_div(P, kClBlock), (unsigned)N), dim3(kClBlock), 0,
-                       stream, (const int64_t*)l.len, (int)P, (const int*)l.rank, labels);
+    hipLaunchKernelGGL(cluster_relabel_kernel, dim3((unsigned)ceil_div(P, kWalkBlock), (unsigned)N), dim3(kWalkBlock), 0,
+                       stream, v.len, (int)P, (const int*)l.rank, labels);
   return check_launch("cluster_dbscan");
 }

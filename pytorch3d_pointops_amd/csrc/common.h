@@ -37,6 +37,9 @@ __device__ __forceinline__ T clamped_length(const int64_t* __restrict__ lengths,
   const int64_t l = lengths[n];
   return (T)(l < 0 ? 0 : (l > P ? P : l));
 }
+// len[n] = clamped_length(lengths, n, P) for the N clouds, on `stream` (radius_walk.hip): for the operators whose every
+// pass reads the lengths, and whose grid_build needs them as an array
+void clamp_lengths_async(const int64_t* lengths, int64_t N, int64_t P, int64_t* len, hipStream_t stream);
 
 // Lays a workspace out as consecutive 256-byte aligned arrays.  With a null base it only sizes (take() returns null):
 // one layout function serves both an operator's *_workspace_bytes query and its entry.

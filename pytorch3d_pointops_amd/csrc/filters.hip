@@ -2,10 +2,10 @@
 // pointops_mask_compact; device half of functions/filters.py).  The definitions are the comment block of the entries in
 // include/pointops_amd.h.  Three kernel groups, every launch stream-ordered, nothing read back, no atomics beyond
 // grid_build's:
-//   radius       lengths (radius_walk.h's kernel), grid_build exactly as cluster.hip calls it (same = true, h_min =
-//                1.001 radius, refine = -1, K = 0) for clouds of kFilterGridMinPoints points and more, then one lane per
-//                point in cell order: radius_walk.h's walk counting the OTHER rows, stopping once the count decides the
-//                mask unless the exact counts are asked for.  POINTOPS_DEBUG=filter_grid=0|1 forces either path.
+//   radius       radius_walk_prepare with cell_radius = radius (the lengths clamped, a grid for clouds of 512 points and
+//                more), then one lane per point in cell order: radius_walk.h's walk counting the OTHER rows, stopping once
+//                the count decides the mask unless the exact counts are asked for.  POINTOPS_DEBUG=filter_grid=0|1 forces
+//                either path.
 //   statistics   rows     one wave per 64 rows, staged through LDS, a lane per row: m_i (filter_stats.h) -> mean_distance
 //                first    one workgroup per chunk of 4096 rows: the chunk's partial of S1 and of n_f
 //                spread   the same geometry: every workgroup adds the chunk partials of its cloud in chunk order -> mean;
@@ -19,18 +19,14 @@
 //                widen    every index sign-extended from its lower half: the offsets are gone
 #include <limits.h>
 
-#include "debug.h"
 #include "filter_stats.h"
-#include "grid.h"
 #include "radius_walk.h"
 #include "wave.h"
 
 namespace pointops {
 
-constexpr float kFilterCellTarget = 2.0f;  // density floor of the cell size (ball query's); the radius usually decides
-constexpr int kFilterGridMinPoints = 512;  // smaller clouds: all pairs (the build's fixed passes cost more)
 constexpr int kCompactBlock = 1024;
-static_assert(kFilterLanes == kClBlock, "one workgroup of the per-point launches is one chunk's lanes");
+static_assert(kFilterLanes == kWalkBlock, "one workgroup of the per-point launches is one chunk's lanes");
 
 // ---------------------------------------------------------------------------------------------------- compaction
 // the upper half of index[n, b]: block b's count, then its offset (little-endian: the halves of an int64)
@@ -82,8 +78,8 @@ __global__ __launch_bounds__(kCompactBlock) void compact_scatter_kernel(const ui
   if (i < P && i >= num_kept[n]) row[2 * i] = -1;
 }
 
-__global__ __launch_bounds__(kClBlock) void compact_widen_kernel(int64_t P, int64_t* index) {
-  const int64_t i = (int64_t)blockIdx.x * kClBlock + threadIdx.x;
+__global__ __launch_bounds__(kWalkBlock) void compact_widen_kernel(int64_t P, int64_t* index) {
+  const int64_t i = (int64_t)blockIdx.x * kWalkBlock + threadIdx.x;
   if (i >= P) return;
   int64_t* const e = index + (int64_t)blockIdx.y * P + i;
   *e = (int64_t)*(const int*)e;
@@ -102,18 +98,17 @@ static void compact_launch(const uint8_t* mask, int64_t N, int64_t P, int64_t* i
   if (P > 0) {
     hipLaunchKernelGGL(compact_scatter_kernel, bgrid, dim3(kCompactBlock), 0, stream, mask, P, index,
                        (const int64_t*)num_kept);
-    hipLaunchKernelGGL(compact_widen_kernel, dim3((unsigned)ceil_div(P, kClBlock), (unsigned)N), dim3(kClBlock), 0,
+    hipLaunchKernelGGL(compact_widen_kernel, dim3((unsigned)ceil_div(P, kWalkBlock), (unsigned)N), dim3(kWalkBlock), 0,
                        stream, P, index);
   }
 }
 
 // ---------------------------------------------------------------------------------------------------- radius
 template <int D>
-__global__ __launch_bounds__(kClBlock) void filter_radius_kernel(ClusterView v, int min_neighbors,
-                                                               uint8_t* __restrict__ mask,
-                                                               int32_t* __restrict__ counts) {
-  GridCloud g = {};
-  const ClusterItem it = cluster_item(v, g);
+__global__ __launch_bounds__(kWalkBlock) void filter_radius_kernel(WalkView v, int min_neighbors,
+                                                                   uint8_t* __restrict__ mask,
+                                                                   int32_t* __restrict__ counts) {
+  const WalkItem it = walk_item(v);
   if (it.t >= v.P) return;
   const int64_t base = (int64_t)it.n * v.P;
   if (it.t >= it.len) {  // padding rows
@@ -121,11 +116,11 @@ __global__ __launch_bounds__(kClBlock) void filter_radius_kernel(ClusterView v, 
     if (counts != nullptr) counts[base + it.t] = 0;
     return;
   }
-  const ClusterLane<D> L = cluster_lane<D>(v, g, it.grid, it.n, it.t);
+  const WalkLane<D> L = walk_lane<D>(v, it);
   const bool exact = counts != nullptr;
   int cnt = 0;
   if (exact || min_neighbors > 0)  // (min_neighbors == 0 is decided before the first step)
-    cluster_walk<D>(v, g, L, it.n, it.len, [&](int j) {
+    radius_walk<D>(v, it, L, [&](int j) {
       if (j != L.i) ++cnt;
       return exact || cnt < min_neighbors;
     });
@@ -133,24 +128,15 @@ __global__ __launch_bounds__(kClBlock) void filter_radius_kernel(ClusterView v, 
   if (exact) counts[base + L.i] = cnt;
 }
 
-// whether the call builds grids (the per-cloud decision is grid_build's, on the device)
-static bool filter_uses_grid(int64_t N, int64_t P) {
-  const long force = debug_knob("filter_grid", -1);  // 0 = never, 1 = whenever the shape allows (tests)
-  if (force == 0 || N <= 0 || P <= 0 || P > knn_grid_max_points()) return false;
-  return force == 1 || P >= kFilterGridMinPoints;
-}
-
 struct RadiusLayout {
-  int64_t* len;  // (N,)
-  char* grid;    // grid_carve's
+  WalkLayout walk;
   size_t bytes;
 };
 
-static RadiusLayout radius_layout(void* ws, int64_t N, int64_t P, bool grid) {
+static RadiusLayout radius_layout(void* ws, int64_t N, int64_t P) {
   Carver c(ws);
   RadiusLayout l;
-  l.len = (int64_t*)c.take(sizeof(int64_t) * (size_t)N);
-  l.grid = c.take(grid ? grid_carve(nullptr, nullptr, N, P, P, kFilterCellTarget) : 0);
+  l.walk = radius_walk_carve(c, "filter_grid", N, P);
   l.bytes = c.off;
   return l;
 }
@@ -266,11 +252,11 @@ __global__ __launch_bounds__(kFilterLanes) void filter_spread_kernel(StatView v,
   if (t == 0) v.part2[(int64_t)n * v.chunks + c] = sum;
 }
 
-__global__ __launch_bounds__(kClBlock) void filter_decide_kernel(StatView v, float std_ratio,
-                                                               const float* __restrict__ mean_distance,
-                                                               double* __restrict__ stats,
-                                                               float* __restrict__ threshold,
-                                                               uint8_t* __restrict__ mask) {
+__global__ __launch_bounds__(kWalkBlock) void filter_decide_kernel(StatView v, float std_ratio,
+                                                                   const float* __restrict__ mean_distance,
+                                                                   double* __restrict__ stats,
+                                                                   float* __restrict__ threshold,
+                                                                   uint8_t* __restrict__ mask) {
   __shared__ float s_thr;
   const int n = blockIdx.y, t = threadIdx.x;
   const int len = clamped_length(v.lengths, n, v.P);
@@ -289,7 +275,7 @@ __global__ __launch_bounds__(kClBlock) void filter_decide_kernel(StatView v, flo
     }
   }
   __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * kClBlock + t;
+  const int64_t i = (int64_t)blockIdx.x * kWalkBlock + t;
   if (i >= v.P) return;
   mask[(int64_t)n * v.P + i] = i < len && filter_keep(mean_distance[(int64_t)n * v.P + i], s_thr) ? 1 : 0;
 }
@@ -333,7 +319,7 @@ extern "C" int pointops_mask_compact(const uint8_t* mask, int64_t N, int64_t P, 
 
 extern "C" size_t pointops_radius_outlier_workspace_bytes(int64_t N, int64_t P) {
   if (!compact_shape_ok(N, P) || N == 0) return 0;
-  return radius_layout(nullptr, N, P, filter_uses_grid(N, P)).bytes;
+  return radius_layout(nullptr, N, P).bytes;
 }
 
 extern "C" int pointops_radius_outlier(const float* points, const int64_t* lengths, int64_t N, int64_t P, int64_t D,
@@ -345,43 +331,19 @@ extern "C" int pointops_radius_outlier(const float* points, const int64_t* lengt
   POINTOPS_REQUIRE(radius > 0.0f && radius <= FLT_MAX && min_neighbors >= 0,
                    "radius_outlier: need a finite radius > 0 and min_neighbors >= 0");
   if (N == 0) return POINTOPS_OK;
-  const bool grid = filter_uses_grid(N, P);
-  const RadiusLayout l = radius_layout(workspace, N, P, grid);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("radius_outlier: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  const RadiusLayout l = radius_layout(workspace, N, P);
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "radius_outlier: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(cluster_lengths_kernel, dim3((unsigned)ceil_div(N, kClBlock)), dim3(kClBlock), 0, stream, lengths,
-                     (int)N, (int)P, l.len);
+  WalkView v;
+  const int rc = radius_walk_prepare(l.walk, points, lengths, N, P, D, radius, stream, &v);
+  if (rc != POINTOPS_OK) return rc;
   if (P > 0) {
-    ClusterView v{};
-    v.points = points;
-    v.len = l.len;
-    v.P = (int)P;
     v.r2 = radius * radius;  // fp32 product, as ball query's radius2
-    if (grid) {
-      GridWs ws;
-      grid_carve(&ws, l.grid, N, P, P, kFilterCellTarget);
-      // K = 0: the build's padding of search rows has nothing to write
-      const KnnArgs a = make_knn_args(points, points, l.len, l.len, N, P, P, D, 0, 0, nullptr, nullptr, stream);
-      GridBuild b{};
-      b.c_target = kFilterCellTarget;
-      b.h_min = radius * 1.001f;
-      b.same = true;
-      b.refine = -1;
-      const int rc = grid_build(a, ws, b);
-      if (rc != POINTOPS_OK) return rc;
-      v.clouds = ws.cloud;
-      v.edges = ws.edges;
-      v.cell_start = ws.cell_start;
-      v.sorted = ws.sorted;
-      v.cell_cap = ws.cell_cap;
-    }
     const int minn = (int)(min_neighbors > INT_MAX ? INT_MAX : min_neighbors);
-    const dim3 pgrid((unsigned)ceil_div(P, kClBlock), (unsigned)N);
+    const dim3 pgrid((unsigned)ceil_div(P, kWalkBlock), (unsigned)N);
     with_exact<3>(Ints<1, 2, 3>{}, (int)D, [&](auto DT) {
-      hipLaunchKernelGGL((filter_radius_kernel<DT>), pgrid, dim3(kClBlock), 0, stream, v, minn, mask, counts);
+      hipLaunchKernelGGL((filter_radius_kernel<DT>), pgrid, dim3(kWalkBlock), 0, stream, v, minn, mask, counts);
     });
   }
   compact_launch(mask, N, P, index, num_kept, stream);
@@ -401,10 +363,8 @@ extern "C" int pointops_statistical_outlier(const float* dists, const int64_t* l
   POINTOPS_REQUIRE(std_ratio >= 0.0f && std_ratio <= FLT_MAX, "statistical_outlier: need a finite std_ratio >= 0");
   if (N == 0) return POINTOPS_OK;
   const StatLayout l = stat_layout(workspace, N, P);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("statistical_outlier: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "statistical_outlier: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   hipStream_t stream = (hipStream_t)stream_;
   StatView v{};
   v.dists = dists;
@@ -416,13 +376,13 @@ extern "C" int pointops_statistical_outlier(const float* dists, const int64_t* l
   v.part2 = l.part2;
   v.partn = l.partn;
   const dim3 cgrid((unsigned)v.chunks, (unsigned)N);
-  const dim3 pgrid((unsigned)(P > 0 ? ceil_div(P, kClBlock) : 1), (unsigned)N);
+  const dim3 pgrid((unsigned)(P > 0 ? ceil_div(P, kWalkBlock) : 1), (unsigned)N);
   if (P > 0)
     hipLaunchKernelGGL(filter_rows_kernel, dim3((unsigned)ceil_div(P, kFilterRowTile), (unsigned)N),
                        dim3(kFilterRowTile), filter_rows_lds(K1), stream, v, mean_distance);
   hipLaunchKernelGGL(filter_first_kernel, cgrid, dim3(kFilterLanes), 0, stream, v, (const float*)mean_distance);
   hipLaunchKernelGGL(filter_spread_kernel, cgrid, dim3(kFilterLanes), 0, stream, v, (const float*)mean_distance);
-  hipLaunchKernelGGL(filter_decide_kernel, pgrid, dim3(kClBlock), 0, stream, v, std_ratio,
+  hipLaunchKernelGGL(filter_decide_kernel, pgrid, dim3(kWalkBlock), 0, stream, v, std_ratio,
                      (const float*)mean_distance, stats, threshold, mask);
   compact_launch(mask, N, P, index, num_kept, stream);
   return check_launch("statistical_outlier");

@@ -5,9 +5,8 @@
 // the keypoints are the local maxima of the saliency within rn, ties to the lower index.
 //
 // A fixed sequence of launches, stream-ordered, nothing read back, no atomics beyond grid_build's:
-//   lengths   the cloud lengths clamped into [0, P] (radius_walk.h's kernel)
-//   grid      grid_build with same = true, h_min = 1.001 max(rs, rn), refine = -1, K = 0, as cluster_dbscan calls it: ONE
-//             grid for both walks -- for clouds of kIssGridMinPoints points and more
+//   prepare   radius_walk_prepare with cell_radius = max(rs, rn): the lengths clamped into [0, P], and for clouds of 512
+//             points and more ONE grid for both walks
 //   saliency  one lane per point in cell order, one full walk with rs: per hit three quantized offsets and nine int64
 //             multiply-adds; then covariance, eigenvalues, decision -> eigenvalues, saliency (and moments) at the
 //             point's own index, and the saliency once more at the lane's position in the cell order
@@ -18,17 +17,13 @@
 // POINTOPS_DEBUG=iss_grid=0|1 forces either path.
 #include <limits.h>
 
-#include "debug.h"
-#include "grid.h"
 #include "iss_saliency.h"
 #include "radius_walk.h"
 #include "small_solvers.h"
 
 namespace pointops {
 
-constexpr float kIssCellTarget = 2.0f;   // density floor of the cell size (ball query's); the radii usually decide
-constexpr int kIssGridMinPoints = 512;   // smaller clouds: all pairs (the build's fixed passes cost more)
-constexpr int kIssMoments = 10;          // n, M1[3], M2[6]
+constexpr int kIssMoments = 10;  // n, M1[3], M2[6]
 
 struct IssParams {
   double s;           // iss_scale(rs)
@@ -36,11 +31,10 @@ struct IssParams {
   int min_neighbors;
 };
 
-__global__ __launch_bounds__(kClBlock) void iss_saliency_kernel(ClusterView v, IssParams p, float* __restrict__ eigenvalues,
-                                                              float* __restrict__ saliency, float* __restrict__ sal_cell,
-                                                              int64_t* __restrict__ moments) {
-  GridCloud g = {};
-  const ClusterItem it = cluster_item(v, g);
+__global__ __launch_bounds__(kWalkBlock) void iss_saliency_kernel(WalkView v, IssParams p, float* __restrict__ eigenvalues,
+                                                                  float* __restrict__ saliency, float* __restrict__ sal_cell,
+                                                                  int64_t* __restrict__ moments) {
+  const WalkItem it = walk_item(v);
   if (it.t >= v.P) return;
   const int64_t base = (int64_t)it.n * v.P;
   if (it.t >= it.len) {  // padding rows
@@ -51,9 +45,9 @@ __global__ __launch_bounds__(kClBlock) void iss_saliency_kernel(ClusterView v, I
       for (int k = 0; k < kIssMoments; ++k) moments[(base + it.t) * kIssMoments + k] = 0;
     return;
   }
-  const ClusterLane<3> L = cluster_lane<3>(v, g, it.grid, it.n, it.t);
+  const WalkLane<3> L = walk_lane<3>(v, it);
   int64_t cnt = 0, M1[3] = {0, 0, 0}, M2[6] = {0, 0, 0, 0, 0, 0};
-  cluster_walk_records<3>(v, g, L, it.n, it.len, [&](int, const float4& c, int) {
+  radius_walk_records<3>(v, it, L, [&](int, const float4& c, int) {
     const int32_t qx = iss_quantize(c.x, L.x, p.s), qy = iss_quantize(c.y, L.y, p.s), qz = iss_quantize(c.z, L.z, p.s);
     ++cnt;
     M1[0] += qx, M1[1] += qy, M1[2] += qz;
@@ -80,23 +74,22 @@ __global__ __launch_bounds__(kClBlock) void iss_saliency_kernel(ClusterView v, I
   }
 }
 
-__global__ __launch_bounds__(kClBlock) void iss_nms_kernel(ClusterView v, IssParams p, const float* __restrict__ saliency,
-                                                         const float* __restrict__ sal_cell,
-                                                         uint8_t* __restrict__ mask) {
-  GridCloud g = {};
-  const ClusterItem it = cluster_item(v, g);
+__global__ __launch_bounds__(kWalkBlock) void iss_nms_kernel(WalkView v, IssParams p, const float* __restrict__ saliency,
+                                                             const float* __restrict__ sal_cell,
+                                                             uint8_t* __restrict__ mask) {
+  const WalkItem it = walk_item(v);
   if (it.t >= v.P) return;
   const int64_t base = (int64_t)it.n * v.P;
   if (it.t >= it.len) {
     mask[base + it.t] = 0;  // padding rows
     return;
   }
-  const ClusterLane<3> L = cluster_lane<3>(v, g, it.grid, it.n, it.t);
+  const WalkLane<3> L = walk_lane<3>(v, it);
   const float si = sal_cell[base + it.t];
   bool keep = si > 0.0f;
   if (keep) {
     int cnt = 0;
-    cluster_walk_records<3>(v, g, L, it.n, it.len, [&](int j, const float4&, int k) {
+    radius_walk_records<3>(v, it, L, [&](int j, const float4&, int k) {
       // (position k of the cell order on the cube path; the raw-cloud path of a cloud WITH a grid has the index only)
       const float sj = k >= 0 ? sal_cell[base + k] : saliency[base + j];
       if (iss_beats(sj, j, si, L.i)) {
@@ -116,26 +109,17 @@ static bool iss_shape_ok(int64_t N, int64_t P) {
   return N >= 0 && N < 65536 && P >= 0 && P <= kIssMaxPoints;
 }
 
-// whether the call builds grids (the per-cloud decision is grid_build's, on the device)
-static bool iss_uses_grid(int64_t N, int64_t P) {
-  const long force = debug_knob("iss_grid", -1);  // 0 = never, 1 = whenever the shape allows (tests)
-  if (force == 0 || N <= 0 || P <= 0 || P > knn_grid_max_points()) return false;
-  return force == 1 || P >= kIssGridMinPoints;
-}
-
 struct IssLayout {
-  int64_t* len;     // (N,)
+  WalkLayout walk;
   float* sal_cell;  // (N, P) the saliency in cell order
-  char* grid;       // grid_carve's
   size_t bytes;
 };
 
-static IssLayout iss_layout(void* ws, int64_t N, int64_t P, bool grid) {
+static IssLayout iss_layout(void* ws, int64_t N, int64_t P) {
   Carver c(ws);
   IssLayout l;
-  l.len = (int64_t*)c.take(sizeof(int64_t) * (size_t)N);
+  l.walk = radius_walk_carve(c, "iss_grid", N, P);
   l.sal_cell = (float*)c.take(sizeof(float) * (size_t)N * (size_t)P);
-  l.grid = c.take(grid ? grid_carve(nullptr, nullptr, N, P, P, kIssCellTarget) : 0);
   l.bytes = c.off;
   return l;
 }
@@ -146,7 +130,7 @@ using namespace pointops;
 
 extern "C" size_t pointops_iss_workspace_bytes(int64_t N, int64_t P) {
   if (!iss_shape_ok(N, P) || N == 0) return 0;
-  return iss_layout(nullptr, N, P, iss_uses_grid(N, P)).bytes;
+  return iss_layout(nullptr, N, P).bytes;
 }
 
 extern "C" int pointops_iss_keypoints(const float* points, const int64_t* lengths, int64_t N, int64_t P,
@@ -161,50 +145,27 @@ extern "C" int pointops_iss_keypoints(const float* points, const int64_t* length
                        min_neighbors >= 0,
                    "iss_keypoints: need finite gamma_21, gamma_32 > 0 and min_neighbors >= 0");
   if (N == 0) return POINTOPS_OK;
-  const bool grid = iss_uses_grid(N, P);
-  const IssLayout l = iss_layout(workspace, N, P, grid);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("iss_keypoints: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  const IssLayout l = iss_layout(workspace, N, P);
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "iss_keypoints: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(cluster_lengths_kernel, dim3((unsigned)ceil_div(N, kClBlock)), dim3(kClBlock), 0, stream, lengths,
-                     (int)N, (int)P, l.len);
+  WalkView vs;
+  const float cell_radius = salient_radius > non_max_radius ? salient_radius : non_max_radius;  // ONE grid, both walks
+  const int rc = radius_walk_prepare(l.walk, points, lengths, N, P, 3, cell_radius, stream, &vs);
+  if (rc != POINTOPS_OK) return rc;
   if (P == 0) return check_launch("iss_keypoints");
-  ClusterView vs{};
-  vs.points = points;
-  vs.len = l.len;
-  vs.P = (int)P;
   vs.r2 = salient_radius * salient_radius;  // fp32 products, as ball query's radius2
-  if (grid) {
-    GridWs ws;
-    grid_carve(&ws, l.grid, N, P, P, kIssCellTarget);
-    // K = 0: the build's padding of search rows has nothing to write
-    const KnnArgs a = make_knn_args(points, points, l.len, l.len, N, P, P, 3, 0, 0, nullptr, nullptr, stream);
-    GridBuild b{};
-    b.c_target = kIssCellTarget;
-    b.h_min = (salient_radius > non_max_radius ? salient_radius : non_max_radius) * 1.001f;
-    b.same = true;
-    b.refine = -1;
-    const int rc = grid_build(a, ws, b);
-    if (rc != POINTOPS_OK) return rc;
-    vs.clouds = ws.cloud;
-    vs.edges = ws.edges;
-    vs.cell_start = ws.cell_start;
-    vs.sorted = ws.sorted;
-    vs.cell_cap = ws.cell_cap;
-  }
-  ClusterView vn = vs;
+  WalkView vn = vs;
   vn.r2 = non_max_radius * non_max_radius;
   IssParams p;
   p.s = iss_scale(salient_radius);
   p.g21 = gamma_21;
   p.g32 = gamma_32;
   p.min_neighbors = (int)(min_neighbors > INT_MAX ? INT_MAX : min_neighbors);
-  const dim3 pgrid((unsigned)ceil_div(P, kClBlock), (unsigned)N);
-  hipLaunchKernelGGL(iss_saliency_kernel, pgrid, dim3(kClBlock), 0, stream, vs, p, eigenvalues, saliency, l.sal_cell,
+  const dim3 pgrid((unsigned)ceil_div(P, kWalkBlock), (unsigned)N);
+  hipLaunchKernelGGL(iss_saliency_kernel, pgrid, dim3(kWalkBlock), 0, stream, vs, p, eigenvalues, saliency, l.sal_cell,
                      moments);
-  hipLaunchKernelGGL(iss_nms_kernel, pgrid, dim3(kClBlock), 0, stream, vn, p, (const float*)saliency,
+  hipLaunchKernelGGL(iss_nms_kernel, pgrid, dim3(kWalkBlock), 0, stream, vn, p, (const float*)saliency,
                      (const float*)l.sal_cell, mask);
   return check_launch("iss_keypoints");
 }

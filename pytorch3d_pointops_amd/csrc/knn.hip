@@ -325,10 +325,9 @@ int pointops_knn_points_idx_reuse(const float* p1, const float* p2, const int64_
   POINTOPS_REQUIRE(N * a.tiles < (1LL << 31), "knn_points_idx: grid too large");
 
   const KnnPlan plan = knn_plan(N, P1, P2, D, K, version);
-  if (!workspace_fits(workspace, workspace_bytes, plan.workspace_bytes)) {
-    set_error("knn_points_idx: workspace of %zu bytes required (got %zu)", plan.workspace_bytes, workspace_bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, plan.workspace_bytes),
+                             "knn_points_idx: workspace of %zu bytes required (got %zu)", plan.workspace_bytes,
+                             workspace_bytes);
   int rc = POINTOPS_OK;
   switch (plan.family) {
     case KnnFamily::kGrid: rc = knn_grid_run(a, norm, workspace, reuse); break;

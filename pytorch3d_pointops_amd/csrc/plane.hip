@@ -360,10 +360,8 @@ extern "C" int pointops_segment_plane(
   }
   if (N == 0) return POINTOPS_OK;
   const PlaneLayout l = plane_layout(workspace, N, P, H);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("segment_plane: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "segment_plane: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   hipStream_t stream = (hipStream_t)stream_;
   const float thr = distance_threshold;
   PlaneCone cone;

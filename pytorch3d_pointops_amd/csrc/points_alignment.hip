@@ -301,10 +301,8 @@ extern "C" int pointops_points_alignment(const float* X, const float* Y, const i
   POINTOPS_REQUIRE(idx != nullptr || P2 == P, "points_alignment: without idx, Y must have P rows per cloud");
   if (N == 0) return POINTOPS_OK;
   const AlignmentLayout l = alignment_layout(workspace, N, P, D, false);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("points_alignment: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "points_alignment: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   return alignment_launch(X, Y, idx, lengths, weights, N, P, P2, D, estimate_scale, allow_reflection, eps, R, T, s,
                           moments, singular_values, l, (hipStream_t)stream_);
 }
@@ -346,10 +344,8 @@ extern "C" int pointops_icp_iteration(const float* X_init, float* Xt, const floa
   POINTOPS_REQUIRE(reuse >= -1 && reuse <= 1, "icp_iteration: reuse is -1 (idx is given), 0 or 1");
   hipStream_t stream = (hipStream_t)stream_;
   const AlignmentLayout l = alignment_layout(workspace, N, P1, D, true);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("icp_iteration: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "icp_iteration: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   if (reuse >= 0) {
     const int rc = pointops_knn_points_idx_reuse(Xt, Y, lengths_x, lengths_y, N, P1, P2, D, 2, 1, -1, idx, dists,
                                                  knn_workspace, knn_workspace_bytes, reuse, stream_);

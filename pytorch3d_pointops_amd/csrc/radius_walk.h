@@ -1,5 +1,5 @@
-// radius_walk.h -- the certified radius walk that cluster.hip and iss.hip share: one lane per point visits every point
-// of its cloud with ball query's `dist2 < r2` (point_dist<D, 2> of grid.h, unfused fp32).
+// radius_walk.h -- the certified radius walk of cluster.hip, iss.hip and filters.hip: one lane per point visits every
+// point of its cloud with ball query's `dist2 < r2` (point_dist<D, 2> of grid.h, unfused fp32).
 //
 // A WALK is ball_grid_lane_kernel's: the nine x-runs of the 3x3x3 cube around the lane's cell, taken only under that
 // kernel's certificate `whole || box_lower_bound<2>(...) >= r2` (every unvisited point has dist2 >= r2).  A lane without
@@ -8,16 +8,17 @@
 // the input alone and never changes a result.  The certificate is per lane and per r2: two walks with two radii over
 // one grid (cells at least as wide as the larger radius) each take their own, from a view with their own r2.
 //
-// cluster_walk_records is the one loop, cluster_walk its index-only form.  The names are cluster.hip's, where this
-// began.
+// The host half (radius_walk.hip) is what an operator does before its own launches: radius_walk_carve takes the walk's
+// part of the operator's workspace, radius_walk_prepare clamps the lengths, builds the grids and fills the view.  The
+// device half: walk_item, walk_lane, then radius_walk_records -- the one loop -- or radius_walk, its index-only form.
 #pragma once
 #include "grid.h"
 
 namespace pointops {
 
-constexpr int kClBlock = 256;
+constexpr int kWalkBlock = 256;  // threads of a per-point launch: grid (ceil(P / kWalkBlock), N)
 
-struct ClusterView {
+struct WalkView {
   const float* points;       // (N, P, D)
   const int64_t* len;        // (N,) clamped
   const GridCloud* clouds;   // grid state: null when the call builds no grid
@@ -25,24 +26,64 @@ struct ClusterView {
   const int* cell_start;
   const float4* sorted;
   int cell_cap, P;
-  float r2;
+  float r2;                  // the caller's: an fp32 product, as ball query's radius2
 };
 
+// ---------------------------------------------------------------------------------------------------- host
+// the walk's part of an operator's workspace
+struct WalkLayout {
+  int64_t* len;  // (N,)
+  char* grid;    // grid_carve's
+  bool uses_grid;
+};
+
+// Takes the walk's arrays from the operator's Carver (sizing only where the Carver's base is null).  Whether the call
+// builds grids is decided here (the per-cloud decision is grid_build's, on the device): `knob` names the operator's
+// debug knob (debug.h), 0 = never, 1 = whenever the shape allows (tests), else by cloud size.
+WalkLayout radius_walk_carve(Carver& c, const char* knob, int64_t N, int64_t P);
+
+// Launches the clamp of `lengths` into l.len and, where the call builds grids, grid_build over cells at least
+// 1.001 cell_radius wide; fills every field of `v` but r2.  Returns grid_build's code.
+int radius_walk_prepare(const WalkLayout& l, const float* points, const int64_t* lengths, int64_t N, int64_t P, int64_t D,
+                        float cell_radius, hipStream_t stream, WalkView* v);
+
+// ---------------------------------------------------------------------------------------------------- device
+// (cloud, lane, length, grid state) of a thread of the per-point launches; g: the cloud's grid where it has one
+struct WalkItem {
+  int n, t, len;
+  bool grid;
+  GridCloud g;
+};
+__device__ __forceinline__ WalkItem walk_item(const WalkView& v) {
+  WalkItem it;
+  it.n = blockIdx.y;
+  it.t = blockIdx.x * kWalkBlock + threadIdx.x;
+  it.len = (int)v.len[it.n];
+  it.grid = false;
+  it.g = {};
+  if (v.clouds != nullptr) {
+    it.g = v.clouds[it.n];
+    it.grid = it.g.use_grid != 0;
+  }
+  return it;
+}
+
 template <int D>
-struct ClusterLane {
+struct WalkLane {
   int i;            // the point's index in its cloud
   float x, y, z;
   bool cube;        // walk the 3x3x3 cube (certified); else the raw cloud
   int cy, cz, X0, X1;
 };
 
-// lane t of cloud n: position t of the cell order where the cloud has a grid, point t where it has none
+// the item's lane: position t of the cell order where the cloud has a grid, point t where it has none (t < len)
 template <int D>
-__device__ __forceinline__ ClusterLane<D> cluster_lane(const ClusterView& v, const GridCloud& g, bool grid, int n,
-                                                       int t) {
-  ClusterLane<D> L;
+__device__ __forceinline__ WalkLane<D> walk_lane(const WalkView& v, const WalkItem& it) {
+  const GridCloud& g = it.g;
+  const int n = it.n, t = it.t;
+  WalkLane<D> L;
   L.cy = L.cz = L.X0 = L.X1 = 0;
-  if (grid) {
+  if (it.grid) {
     const float4 q = v.sorted[(int64_t)n * (v.P + kSortedPad) + t];
     L.x = q.x, L.y = q.y, L.z = q.z;
     L.i = __float_as_int(q.w);
@@ -66,8 +107,9 @@ __device__ __forceinline__ ClusterLane<D> cluster_lane(const ClusterView& v, con
 // fn(j, c, k) for every neighbour j of the lane (dist2 < r2, the lane itself included), until fn returns false: c its
 // coordinates, k its position in the cloud's cell order -- or -1 on the raw-cloud path, which has none
 template <int D, typename Fn>
-__device__ __forceinline__ void cluster_walk_records(const ClusterView& v, const GridCloud& g, const ClusterLane<D>& L,
-                                                     int n, int len, Fn fn) {
+__device__ __forceinline__ void radius_walk_records(const WalkView& v, const WalkItem& it, const WalkLane<D>& L, Fn fn) {
+  const GridCloud& g = it.g;
+  const int n = it.n, len = it.len;
   if (L.cube) {
     const float4* __restrict__ sp = v.sorted + (int64_t)n * (v.P + kSortedPad);
     const int* __restrict__ cstart = v.cell_start + (int64_t)n * (v.cell_cap + 1);
@@ -101,36 +143,8 @@ __device__ __forceinline__ void cluster_walk_records(const ClusterView& v, const
 
 // fn(j) for every neighbour j of the lane (dist2 < r2, the lane itself included), until fn returns false
 template <int D, typename Fn>
-__device__ __forceinline__ void cluster_walk(const ClusterView& v, const GridCloud& g, const ClusterLane<D>& L, int n,
-                                             int len, Fn fn) {
-  cluster_walk_records<D>(v, g, L, n, len, [&](int j, const float4&, int) { return fn(j); });
-}
-
-// (cloud, lane, length, grid state) of a thread of the per-point launches; false: nothing to walk
-struct ClusterItem {
-  int n, t, len;
-  bool grid;
-};
-__device__ __forceinline__ ClusterItem cluster_item(const ClusterView& v, GridCloud& g) {
-  ClusterItem it;
-  it.n = blockIdx.y;
-  it.t = blockIdx.x * kClBlock + threadIdx.x;
-  it.len = (int)v.len[it.n];
-  it.grid = false;
-  if (v.clouds != nullptr) {
-    g = v.clouds[it.n];
-    it.grid = g.use_grid != 0;
-  }
-  return it;
-}
-
-// (static: a kernel that is no template, in a header of two translation units)
-static __global__ __launch_bounds__(kClBlock) void cluster_lengths_kernel(const int64_t* __restrict__ lengths, int N,
-                                                                        int P, int64_t* __restrict__ len) {
-  const int n = blockIdx.x * kClBlock + threadIdx.x;
-  if (n >= N) return;
-  const int64_t l = lengths != nullptr ? lengths[n] : (int64_t)P;
-  len[n] = l < 0 ? 0 : (l > P ? P : l);
+__device__ __forceinline__ void radius_walk(const WalkView& v, const WalkItem& it, const WalkLane<D>& L, Fn fn) {
+  radius_walk_records<D>(v, it, L, [&](int j, const float4&, int) { return fn(j); });
 }
 
 }  // namespace pointops

@@ -358,10 +358,8 @@ extern "C" int pointops_ransac_alignment(
   POINTOPS_REQUIRE(refine_steps >= 0 && first_cloud >= 0, "ransac_alignment: need refine_steps >= 0, first_cloud >= 0");
   if (N == 0) return POINTOPS_OK;
   const RansacLayout l = ransac_layout(workspace, N, P1, H);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("ransac_alignment: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "ransac_alignment: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   hipStream_t stream = (hipStream_t)stream_;
   const float thr2 = inlier_threshold * inlier_threshold;
   const float q = edge_length_ratio * edge_length_ratio;

@@ -355,18 +355,16 @@ extern "C" int pointops_registration_step(
                    "registration_step: max_correspondence_distance must be finite and > 0");
   hipStream_t stream = (hipStream_t)stream_;
   const RegistrationLayout l = registration_layout(workspace, N, P1);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("registration_step: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "registration_step: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   POINTOPS_REQUIRE(search_version == -1 || pointops_knn_check_version(search_version, 3, 1),
                    "registration_step: search_version is -1 or a version of knn_points valid for D = 3, K = 1");
   const int version = search_version;
   const size_t knn_need = pointops_knn_workspace_bytes(N, P1, P2, 3, 1, version);
-  if (!workspace_fits(knn_workspace, knn_workspace_bytes, knn_need)) {  // (before anything is launched)
-    set_error("registration_step: search workspace of %zu bytes, need %zu", knn_workspace_bytes, knn_need);
-    return POINTOPS_EWORKSPACE;
-  }
+  // (before anything is launched)
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(knn_workspace, knn_workspace_bytes, knn_need),
+                             "registration_step: search workspace of %zu bytes, need %zu", knn_workspace_bytes,
+                             knn_need);
   const int nb = pa_blocks(P1);
   const dim3 rows((unsigned)nb, (unsigned)N);
   if (first) {

@@ -4,7 +4,7 @@
 // its members' points and features, summed in fp64 in an order that the sorted position alone fixes.
 //
 // A fixed sequence of launches, stream-ordered, nothing read back, no atomics on floating-point data:
-//   lengths   the cloud lengths clamped into [0, P] (radius_walk.h's kernel)
+//   lengths   the cloud lengths clamped into [0, P] (common.h's clamp_lengths_async)
 //   bounds    fp32 min / max over the live rows, one slot per workgroup of 2048 rows (grid_build's bounding-box scheme:
 //             no atomics, nothing to initialise; here non-finite rows are left out)
 //   frame     one wave per cloud reduces the slots; voxel_key.h's voxel_frame decides origin, c_lo and status
@@ -28,7 +28,6 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "debug.h"
-#include "radius_walk.h"
 #include "voxel_key.h"
 #include "wave.h"
 
@@ -507,13 +506,10 @@ extern "C" int pointops_voxel_downsample(const float* points, const int64_t* len
     return check_launch("voxel_downsample");
   }
   const VoxelLayout l = voxel_layout(workspace, N, P);
-  if (!workspace_fits(workspace, workspace_bytes, l.bytes)) {
-    set_error("voxel_downsample: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-    return POINTOPS_EWORKSPACE;
-  }
+  POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
+                             "voxel_downsample: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
   const size_t T = (size_t)N * (size_t)P;
-  hipLaunchKernelGGL(cluster_lengths_kernel, dim3((unsigned)ceil_div(N, kClBlock)), dim3(kClBlock), 0, stream, lengths,
-                     (int)N, (int)P, l.len);
+  clamp_lengths_async(lengths, N, P, l.len, stream);
   hipLaunchKernelGGL(voxel_bounds_kernel, dim3((unsigned)l.nslots, (unsigned)N), dim3(kVoxelBlock), 0, stream, points,
                      (const int64_t*)l.len, (int)P, l.slots);
   hipLaunchKernelGGL(voxel_frame_kernel, dim3((unsigned)N), dim3(kWave), 0, stream, (const float*)l.slots, l.nslots,

@@ -196,7 +196,56 @@ def test_fuzz_iss_keypoints(dev, monkeypatch, seed):
           knobs=("iss_grid=0", "iss_grid=1"), alone=lambda c: c.lengths, public=public)
 
 
+def _two_small_clouds(P, ragged):
+    """N = 2 uniform clouds of P rows, lengths None or (0, P); a radius whose ball holds about 4 of a cloud's points, or
+    the whole unit cube where there are no 4 (the pair of P = 2 are neighbours)."""
+    rng = np.random.default_rng(70 + P)
+    pts = np.stack([gen.cloud(rng, "uniform", P, 3) for _ in range(2)])
+    lengths = np.array([0, P], np.int64) if ragged else None
+    if ragged:
+        pts[0] = gen.PAD
+    return pts, lengths, 2.0 if P < 4 else float(np.float32(gen.radius_for(4.0, P, 3)))
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["full", "ragged"])
+@pytest.mark.parametrize("P", [1, 2, 65])
+def test_radius_family_on_two_small_clouds_with_and_without_a_grid(dev, monkeypatch, P, ragged):
+    """The shapes below everything the cases above draw: one point, a pair, one lane past a wave; `lengths` absent (the
+    clamp's null path) or with an empty cloud.  Each operator equals its checker under *_grid=0 and under *_grid=1,
+    where P = 1 is the smallest grid there is."""
+    from pytorch3d_pointops_amd import _C_iss
+    from pytorch3d_pointops_amd import functions as f
+
+    pts, lengths, radius = _two_small_clouds(P, ragged)
+    rn, mp, g = float(np.float32(0.6 * radius)), 2, 0.975
+    p, L = _T(pts, dev), _T(lengths, dev)
+    want_cluster = cluster_ref.dbscan(pts, lengths, radius, mp)
+    want_radius = filters_ref.radius(pts, lengths, radius, mp)
+    for value in (0, 1):
+        what = f"N = 2, P = {P}, lengths {None if lengths is None else lengths.tolist()}, *_grid={value}"
+        monkeypatch.setenv("POINTOPS_DEBUG", f"cluster_grid={value},filter_grid={value},iss_grid={value}")
+        r = f.cluster_dbscan(p, radius, mp, lengths=L)
+        assert_cluster_equal((_np(r.labels), _np(r.num_clusters), _np(r.core_mask)), want_cluster, what)
+        r = f.remove_radius_outlier(p, L, radius=radius, min_neighbors=mp, return_counts=True)
+        assert_filters_equal({k: _np(getattr(r, k)) for k in RADIUS_KEYS}, want_radius, RADIUS_KEYS, what)
+        out = _C_iss.iss_keypoints(p, L, radius, rn, g, g, mp, want_moments=True)
+        check_iss_stages(dict(zip(ISS_KEYS, (_np(x) for x in out))), None, (pts, lengths, radius, rn, g, g, mp), what)
+
+
 # ------------------------------------------------------------------------------------------------ voxel_downsample
+@pytest.mark.parametrize("P", [1, 2, 65])
+def test_voxel_downsample_on_two_small_clouds_without_lengths(dev, P):
+    """The null `lengths` of the shared clamp, at the shapes of the test above."""
+    from pytorch3d_pointops_amd import functions as f
+
+    pts = _two_small_clouds(P, False)[0]
+    scene = (pts, None, 0.3, None, None)
+    r = f.voxel_downsample(_T(pts, dev), None, voxel_size=0.3)
+    out = dict(num_voxels=r.num_voxels, status=r.status, inverse=r.inverse, counts=r.counts,
+               first_index=r.first_index, coords=r.coords, centroids=r.points, pooled=r.features)
+    check_voxel_stages({k: _np(out[k]) for k in VOXEL_KEYS}, scene, voxel_ref.downsample(*scene), f"N = 2, P = {P}")
+
+
 @pytest.mark.parametrize("seed", gen.SEEDS)
 def test_fuzz_voxel_downsample(dev, monkeypatch, seed):
     from pytorch3d_pointops_amd import functions as f
