@@ -1,5 +1,6 @@
 // block_sum.h -- the fp64 block reduction of the per-cloud moment passes (points_alignment.hip, registration.hip): DPP
-// wave sums, the four waves of a block through LDS, one partial per block.  No atomics: the order of every sum is fixed
+// wave sums, the four waves of a block through LDS, one partial per block (pa_block_sum), and the ascending sum of a
+// cloud's partials in the one-wave solve kernels (pa_sum_partials).  No atomics: the order of every sum is fixed
 // by the row index and the launch shape, so results are bit-reproducible.
 #pragma once
 #include "common.h"
@@ -51,6 +52,27 @@ __device__ __forceinline__ void pa_block_sum(const double (&acc)[M], double (*s_
     for (int w = 1; w < kPaWaves; ++w) v += s_part[w][threadIdx.x];
     out[threadIdx.x] = v;
   }
+}
+
+// The other end, in the one-wave solve kernels: lane m < M adds partial m of the cloud's nb blocks (cloud_partials:
+// [nb][M]) in ascending block order -- the same sum in every run -- into s_mom[m] and, where given, moments_out[m].
+// A cloud that is not `live` (registration: frozen) sums nothing and reports zeros.  Every thread of the block calls it;
+// s_mom is complete when it returns.
+template <int M>
+__device__ __forceinline__ void pa_sum_partials(const double* __restrict__ cloud_partials, int nb, bool live,
+                                                double* s_mom, double* __restrict__ moments_out) {
+  static_assert(M <= kWave, "one lane per moment");
+  if ((int)threadIdx.x < M) {
+    double v = 0.0;
+    if (live) {
+      const double* __restrict__ src = cloud_partials + threadIdx.x;
+#pragma unroll 8
+      for (int b = 0; b < nb; ++b) v += src[(int64_t)b * M];
+    }
+    s_mom[threadIdx.x] = v;
+    if (moments_out != nullptr) moments_out[threadIdx.x] = v;
+  }
+  __syncthreads();
 }
 
 }  // namespace pointops

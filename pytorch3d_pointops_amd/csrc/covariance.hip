@@ -5,194 +5,69 @@
 // at K = 16, D = 3) next to the centred copy of the neighbourhood:
 //     m = mean_k x_k ;  cov[a][b] = mean_k (x_k[a] - m[a]) (x_k[b] - m[b]).
 // Here one lane owns one point: the K x D neighbourhood row (contiguous, K*D*4 bytes) is read
-// twice from L1/L2 (mean pass, covariance pass), the D x D accumulators live in registers, and
-// only the (N,P,D,D) result is written.  Backward (closed form, the mean terms cancel because
-// sum_k (x_k - m) = 0):  grad_x_k = (G + G^T) (x_k - m) / K.
+// twice (mean pass, covariance pass), the D x D accumulators live in registers, and only the
+// (N,P,D,D) result is written.  Backward (closed form):  grad_x_k = (G + G^T) (x_k - m) / K.
+// The three passes are neighbourhood_sums.h's, which local_frames.hip calls as well; this file is
+// where a lane's row lives and how it gets there.
 // fp32 throughout; sums run in k order (the torch reduction order is unspecified: parity within 1e-5).
 #include "common.h"
+#include "neighbourhood_sums.h"
 
 namespace pointops {
 
-constexpr int kCovBlock = 256;
+constexpr int kCovBlock = 256;  // rows per workgroup of the direct form
 constexpr int kCovMaxD = 8;
-
-template <int DT>  // DT = compile-time D (2, 3) or 0 = runtime D <= kCovMaxD
-__global__ __launch_bounds__(kCovBlock) void covariance_kernel(const float* __restrict__ knn, int64_t rows, int K,
-                                                              int Drt, float* __restrict__ cov) {
-  constexpr int DM = DT > 0 ? DT : kCovMaxD;
-  const int D = DT > 0 ? DT : Drt;
-  const int64_t r = (int64_t)blockIdx.x * kCovBlock + threadIdx.x;
-  if (r >= rows) return;
-  const float* __restrict__ x = knn + r * K * D;
-  const float inv_k = 1.0f / (float)K;
-  float m[DM];
-#pragma unroll
-  for (int d = 0; d < DM; ++d) m[d] = 0.0f;
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int d = 0; d < DM; ++d)
-      if (d < D) m[d] += x[k * D + d];
-  }
-#pragma unroll
-  for (int d = 0; d < DM; ++d) m[d] *= inv_k;
-  float c[DM][DM];
-#pragma unroll
-  for (int a = 0; a < DM; ++a)
-#pragma unroll
-    for (int b = 0; b < DM; ++b) c[a][b] = 0.0f;
-  for (int k = 0; k < K; ++k) {
-    float v[DM];
-#pragma unroll
-    for (int d = 0; d < DM; ++d) v[d] = d < D ? x[k * D + d] - m[d] : 0.0f;
-#pragma unroll
-    for (int a = 0; a < DM; ++a)
-#pragma unroll
-      for (int b = 0; b < DM; ++b)
-        if (a < D && b < D) c[a][b] += v[a] * v[b];
-  }
-  float* __restrict__ o = cov + r * D * D;
-#pragma unroll
-  for (int a = 0; a < DM; ++a)
-#pragma unroll
-    for (int b = 0; b < DM; ++b)
-      if (a < D && b < D) o[a * D + b] = c[a][b] * inv_k;
-}
-
-template <int DT>
-__global__ __launch_bounds__(kCovBlock) void covariance_backward_kernel(const float* __restrict__ knn,
-                                                                       const float* __restrict__ grad_cov,
-                                                                       int64_t rows, int K, int Drt,
-                                                                       float* __restrict__ grad_knn) {
-  constexpr int DM = DT > 0 ? DT : kCovMaxD;
-  const int D = DT > 0 ? DT : Drt;
-  const int64_t r = (int64_t)blockIdx.x * kCovBlock + threadIdx.x;
-  if (r >= rows) return;
-  const float* __restrict__ x = knn + r * K * D;
-  const float* __restrict__ g = grad_cov + r * D * D;
-  float* __restrict__ o = grad_knn + r * K * D;
-  const float inv_k = 1.0f / (float)K;
-  float m[DM];
-#pragma unroll
-  for (int d = 0; d < DM; ++d) m[d] = 0.0f;
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int d = 0; d < DM; ++d)
-      if (d < D) m[d] += x[k * D + d];
-  }
-#pragma unroll
-  for (int d = 0; d < DM; ++d) m[d] *= inv_k;
-  float s[DM][DM];  // (G + G^T) / K
-#pragma unroll
-  for (int a = 0; a < DM; ++a)
-#pragma unroll
-    for (int b = 0; b < DM; ++b) s[a][b] = (a < D && b < D) ? (g[a * D + b] + g[b * D + a]) * inv_k : 0.0f;
-  for (int k = 0; k < K; ++k) {
-    float v[DM];
-#pragma unroll
-    for (int d = 0; d < DM; ++d) v[d] = d < D ? x[k * D + d] - m[d] : 0.0f;
-#pragma unroll
-    for (int a = 0; a < DM; ++a) {
-      if (a < D) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int b = 0; b < DM; ++b) acc += s[a][b] * v[b];
-        o[k * D + a] = acc;
-      }
-    }
-  }
-}
-
-
 // Staged form for K * D <= 64: a 128-lane workgroup loads its 128 neighbourhood rows COALESCED into
 // LDS (row stride K*D + 1 words: conflict-free for the per-lane walk), then every lane makes both
-// passes over its own row from LDS -- the direct kernels above read one 4..256-byte row per lane
-// with 64 cache lines per wave instruction (0.26 ms for 8 x 65536 x 16 x 3, no faster than the five
-// torch kernels they replace).
+// passes over its own row from LDS; the backward writes its results back in place, so that the global
+// store is coalesced as well.  The direct form reads one 4..256-byte row per lane from L1/L2 with
+// 64 cache lines per wave instruction (0.26 ms for 8 x 65536 x 16 x 3, no faster than the five
+// torch kernels it replaces).
 constexpr int kCovTile = 128;
 constexpr int kCovStageMax = 64;  // floats per row
 
-template <int DT, bool BACKWARD>
-__global__ __launch_bounds__(kCovTile) void covariance_staged_kernel(const float* __restrict__ knn,
-                                                                    const float* __restrict__ grad_cov,
-                                                                    int64_t rows, int K, int Drt,
-                                                                    float* __restrict__ out) {
-  extern __shared__ float s_x[];  // [kCovTile][K*D + 1]
+template <int DT, bool BACKWARD, bool STAGED>  // DT = compile-time D (2, 3) or 0 = runtime D <= kCovMaxD
+__global__ __launch_bounds__(STAGED ? kCovTile : kCovBlock) void covariance_kernel(const float* __restrict__ knn,
+                                                                                  const float* __restrict__ grad_cov,
+                                                                                  int64_t rows, int K, int Drt,
+                                                                                  float* __restrict__ out) {
+  extern __shared__ float s_x[];  // STAGED: [kCovTile][K*D + 1]
   constexpr int DM = DT > 0 ? DT : kCovMaxD;
+  constexpr int kRows = STAGED ? kCovTile : kCovBlock;
   const int D = DT > 0 ? DT : Drt;
-  const int T = K * D, stride = T + 1;
-  const int64_t row0 = (int64_t)blockIdx.x * kCovTile;
-  const int nrows = (int)min((int64_t)kCovTile, rows - row0);
-  const float* __restrict__ src = knn + row0 * T;
-  for (int f = threadIdx.x; f < nrows * T; f += kCovTile) {
-    const int r = f / T;
-    s_x[r * stride + (f - r * T)] = src[f];
+  const int T = STAGED ? K * D : 0, stride = T + 1;  // floats of a staged row (K * D <= kCovStageMax) and its stride
+  const int64_t row0 = (int64_t)blockIdx.x * kRows;
+  const int nrows = (int)min((int64_t)kRows, rows - row0);
+  if constexpr (STAGED) {
+    const float* __restrict__ src = knn + row0 * T;
+    for (int f = threadIdx.x; f < nrows * T; f += kCovTile) {
+      const int r = f / T;
+      s_x[r * stride + (f - r * T)] = src[f];
+    }
+    __syncthreads();
   }
-  __syncthreads();
   const bool active = (int)threadIdx.x < nrows;
-  if (!BACKWARD && !active) return;  // the backward form has one more barrier: every lane must reach it
+  if (!(STAGED && BACKWARD) && !active) return;  // the staged backward has one more barrier: every lane must reach it
   if (active) {
-  const float* __restrict__ x = s_x + threadIdx.x * stride;
-  const int64_t r = row0 + threadIdx.x;
-  const float inv_k = 1.0f / (float)K;
-  float m[DM];
-#pragma unroll
-  for (int d = 0; d < DM; ++d) m[d] = 0.0f;
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int d = 0; d < DM; ++d)
-      if (d < D) m[d] += x[k * D + d];
-  }
-#pragma unroll
-  for (int d = 0; d < DM; ++d) m[d] *= inv_k;
-  if constexpr (!BACKWARD) {
-    float c[DM][DM];
-#pragma unroll
-    for (int a = 0; a < DM; ++a)
-#pragma unroll
-      for (int b = 0; b < DM; ++b) c[a][b] = 0.0f;
-    for (int k = 0; k < K; ++k) {
-      float v[DM];
-#pragma unroll
-      for (int d = 0; d < DM; ++d) v[d] = d < D ? x[k * D + d] - m[d] : 0.0f;
+    const int64_t r = row0 + threadIdx.x;
+    // the lane's LDS row, read by the passes and written in place by the backward (formed but never used when direct)
+    float* mine = s_x + threadIdx.x * stride;
+    const float* x = STAGED ? mine : knn + r * K * D;
+    auto row = [&](int k) { return x + k * D; };
+    if constexpr (!BACKWARD) {
+      float c[DM][DM];
+      nb_covariance<DM>(row, K, D, c);
+      float* __restrict__ o = out + r * D * D;
 #pragma unroll
       for (int a = 0; a < DM; ++a)
 #pragma unroll
         for (int b = 0; b < DM; ++b)
-          if (a < D && b < D) c[a][b] += v[a] * v[b];
-    }
-    float* __restrict__ o = out + r * D * D;
-#pragma unroll
-    for (int a = 0; a < DM; ++a)
-#pragma unroll
-      for (int b = 0; b < DM; ++b)
-        if (a < D && b < D) o[a * D + b] = c[a][b] * inv_k;
-  } else {
-    const float* __restrict__ g = grad_cov + r * D * D;
-    float sm[DM][DM];  // (G + G^T) / K
-#pragma unroll
-    for (int a = 0; a < DM; ++a)
-#pragma unroll
-      for (int b = 0; b < DM; ++b) sm[a][b] = (a < D && b < D) ? (g[a * D + b] + g[b * D + a]) * inv_k : 0.0f;
-    // results go back through LDS (in place) so that the global store is coalesced as well
-    float* __restrict__ xo = s_x + threadIdx.x * stride;
-    for (int k = 0; k < K; ++k) {
-      float v[DM], w[DM];
-#pragma unroll
-      for (int d = 0; d < DM; ++d) v[d] = d < D ? xo[k * D + d] - m[d] : 0.0f;
-#pragma unroll
-      for (int a = 0; a < DM; ++a) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int b = 0; b < DM; ++b) acc += sm[a][b] * v[b];
-        w[a] = acc;
-      }
-#pragma unroll
-      for (int a = 0; a < DM; ++a)
-        if (a < D) xo[k * D + a] = w[a];
+          if (a < D && b < D) o[a * D + b] = c[a][b];
+    } else {
+      nb_covariance_backward<DM>(row, K, D, grad_cov + r * D * D, STAGED ? mine : out + r * K * D);
     }
   }
-  }  // active
-  if constexpr (BACKWARD) {
+  if constexpr (STAGED && BACKWARD) {
     __syncthreads();
     float* __restrict__ dst = out + row0 * T;
     for (int f = threadIdx.x; f < nrows * T; f += kCovTile) {
@@ -202,57 +77,41 @@ __global__ __launch_bounds__(kCovTile) void covariance_staged_kernel(const float
   }
 }
 
+// out = cov (N,P,D,D) of the forward, grad_knn (N,P,K,D) of the backward
+template <bool BACKWARD>
+static int covariance_launch(const char* what, const float* knn, const float* grad_cov, int64_t N, int64_t P, int64_t K,
+                             int64_t D, float* out, void* stream_) {
+  POINTOPS_REQUIRE(N >= 0 && P >= 0 && K >= 1 && D >= 1 && D <= kCovMaxD && K < (1LL << 31),
+                   "%s: need K >= 1 and 1 <= D <= %d", what, kCovMaxD);
+  const int64_t rows = N * P;
+  if (rows == 0) return POINTOPS_OK;
+  POINTOPS_REQUIRE(ceil_div(rows, kCovBlock) < (1LL << 31), "%s: grid too large", what);
+  hipStream_t stream = (hipStream_t)stream_;
+  const bool staged = K * D <= kCovStageMax;
+  const dim3 grid((unsigned)ceil_div(rows, staged ? kCovTile : kCovBlock)), block(staged ? kCovTile : kCovBlock);
+  const size_t lds = staged ? sizeof(float) * (size_t)kCovTile * (size_t)(K * D + 1) : 0;
+  with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
+    if (staged) {
+      hipLaunchKernelGGL((covariance_kernel<DT, BACKWARD, true>), grid, block, lds, stream, knn, grad_cov, rows, (int)K,
+                         (int)D, out);
+    } else {
+      hipLaunchKernelGGL((covariance_kernel<DT, BACKWARD, false>), grid, block, lds, stream, knn, grad_cov, rows,
+                         (int)K, (int)D, out);
+    }
+  });
+  return check_launch(what);
+}
+
 }  // namespace pointops
 
 using namespace pointops;
 
 extern "C" int pointops_point_covariances(const float* knn, int64_t N, int64_t P, int64_t K, int64_t D, float* cov,
                                           void* stream_) {
-  POINTOPS_REQUIRE(N >= 0 && P >= 0 && K >= 1 && D >= 1 && D <= kCovMaxD && K < (1LL << 31),
-                   "point_covariances: need K >= 1 and 1 <= D <= %d", kCovMaxD);
-  const int64_t rows = N * P;
-  if (rows == 0) return POINTOPS_OK;
-  const int64_t blocks = ceil_div(rows, kCovBlock);
-  POINTOPS_REQUIRE(blocks < (1LL << 31), "point_covariances: grid too large");
-  hipStream_t stream = (hipStream_t)stream_;
-  if (K * D <= kCovStageMax) {
-    const dim3 gs((unsigned)ceil_div(rows, kCovTile)), bs(kCovTile);
-    const size_t lds = sizeof(float) * (size_t)kCovTile * (size_t)(K * D + 1);
-    with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
-      hipLaunchKernelGGL((covariance_staged_kernel<DT, false>), gs, bs, lds, stream, knn, nullptr, rows, (int)K, (int)D,
-                         cov);
-    });
-    return check_launch("point_covariances");
-  }
-  const dim3 grid((unsigned)blocks), block(kCovBlock);
-  with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
-    hipLaunchKernelGGL(covariance_kernel<DT>, grid, block, 0, stream, knn, rows, (int)K, (int)D, cov);
-  });
-  return check_launch("point_covariances");
+  return covariance_launch<false>("point_covariances", knn, nullptr, N, P, K, D, cov, stream_);
 }
 
 extern "C" int pointops_point_covariances_backward(const float* knn, const float* grad_cov, int64_t N, int64_t P,
                                                    int64_t K, int64_t D, float* grad_knn, void* stream_) {
-  POINTOPS_REQUIRE(N >= 0 && P >= 0 && K >= 1 && D >= 1 && D <= kCovMaxD && K < (1LL << 31),
-                   "point_covariances_backward: need K >= 1 and 1 <= D <= %d", kCovMaxD);
-  const int64_t rows = N * P;
-  if (rows == 0) return POINTOPS_OK;
-  const int64_t blocks = ceil_div(rows, kCovBlock);
-  POINTOPS_REQUIRE(blocks < (1LL << 31), "point_covariances_backward: grid too large");
-  hipStream_t stream = (hipStream_t)stream_;
-  if (K * D <= kCovStageMax) {
-    const dim3 gs((unsigned)ceil_div(rows, kCovTile)), bs(kCovTile);
-    const size_t lds = sizeof(float) * (size_t)kCovTile * (size_t)(K * D + 1);
-    with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
-      hipLaunchKernelGGL((covariance_staged_kernel<DT, true>), gs, bs, lds, stream, knn, grad_cov, rows, (int)K, (int)D,
-                         grad_knn);
-    });
-    return check_launch("point_covariances_backward");
-  }
-  const dim3 grid((unsigned)blocks), block(kCovBlock);
-  with_exact<0>(Ints<3, 2>{}, (int)D, [&](auto DT) {
-    hipLaunchKernelGGL(covariance_backward_kernel<DT>, grid, block, 0, stream, knn, grad_cov, rows, (int)K, (int)D,
-                       grad_knn);
-  });
-  return check_launch("point_covariances_backward");
+  return covariance_launch<true>("point_covariances_backward", knn, grad_cov, N, P, K, D, grad_knn, stream_);
 }

@@ -19,6 +19,7 @@
 // No atomics on global memory, no workspace, a fixed summation order.
 #include "common.h"
 #include "debug.h"
+#include "small_solvers.h"
 
 namespace pointops {
 
@@ -37,16 +38,6 @@ constexpr float kC1F = (float)(11.0 / (2.0 * 3.14159265358979323846));
 __device__ __forceinline__ int fpfh_bin(float f, float off, float scale) {
   const float x = floorf((f + off) * scale);
   return (int)fminf(fmaxf(x, 0.0f), 10.0f);
-}
-
-__device__ __forceinline__ float dot3f(const float (&a)[3], const float (&b)[3]) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-
-__device__ __forceinline__ void cross3f(const float (&a)[3], const float (&b)[3], float (&o)[3]) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 template <int G>

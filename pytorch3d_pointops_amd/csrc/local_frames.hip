@@ -6,8 +6,8 @@
 // third time for the sign disambiguation.  Here one lane owns one query point i of cloud n:
 //   1. the K neighbour rows x_k = points[n, idx[n,i,k]] (zero where k >= lengths[n] or idx is out of range, like
 //      gather_neighbors with lengths);
-//   2. m = mean_k x_k, C = mean_k (x_k - m)(x_k - m)^T in fp32, in covariance.hip's k-ascending order: C is
-//      bit-equal to point_covariances(gather_neighbors(points, idx, lengths));
+//   2. m = mean_k x_k, C = mean_k (x_k - m)(x_k - m)^T in fp32, by the functions of neighbourhood_sums.h that
+//      covariance.hip calls: C is bit-equal to point_covariances(gather_neighbors(points, idx, lengths));
 //   3. cyclic Jacobi in fp64 on C, eigenpairs sorted ascending (stable: a zero C gives the identity frame), rounded
 //      to fp32 -- curvatures = eigenvalues, frame columns = eigenvectors (v0, v1, v2);
 //   4. with `disambiguate`: v0 -> n and v2 -> z are flipped when fewer than K/2 neighbours have (x_k - x_i).v > 0,
@@ -24,6 +24,7 @@
 // v_j v_i^T -- the eigh backward; the flips are piecewise constant.  Coincident eigenvalues divide by zero, as
 // torch.linalg.eigh's backward does.  The rest of the chain (gather, covariance backward, scatter) is existing code.
 #include "common.h"
+#include "neighbourhood_sums.h"
 #include "small_solvers.h"
 
 namespace pointops {
@@ -76,49 +77,24 @@ __global__ __launch_bounds__(kLfTile) void local_frames_kernel(const float* __re
   }
   const float* __restrict__ sx = s_x + threadIdx.x * stride;
   const int64_t* __restrict__ my_idx = idx0 + (int64_t)threadIdx.x * K;
-  auto neighbour = [&](int k, float (&x)[3]) {
+  auto neighbour = [&](int k) {
+    NbRow<3> x;
     if constexpr (STAGED) {
 #pragma unroll
-      for (int d = 0; d < 3; ++d) x[d] = sx[3 * k + d];
+      for (int d = 0; d < 3; ++d) x.v[d] = sx[3 * k + d];
     } else {
       const int64_t j = my_idx[k];
       const bool ok = j >= 0 && j < P && (int64_t)k < len;
       const float* __restrict__ src = pts + (ok ? j : 0) * 3;
 #pragma unroll
-      for (int d = 0; d < 3; ++d) x[d] = ok ? src[d] : 0.0f;
+      for (int d = 0; d < 3; ++d) x.v[d] = ok ? src[d] : 0.0f;
     }
+    return x;
   };
 
-  // mean and covariance: covariance.hip's operations in its order
-  const float inv_k = 1.0f / (float)K;
-  float m[3] = {0.0f, 0.0f, 0.0f};
-  for (int k = 0; k < K; ++k) {
-    float x[3];
-    neighbour(k, x);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) m[d] += x[d];
-  }
-#pragma unroll
-  for (int d = 0; d < 3; ++d) m[d] *= inv_k;
+  // mean and covariance: neighbourhood_sums.h's, the functions covariance.hip calls
   float c[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) c[a][b] = 0.0f;
-  for (int k = 0; k < K; ++k) {
-    float x[3], v[3];
-    neighbour(k, x);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) v[d] = x[d] - m[d];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) c[a][b] += v[a] * v[b];
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) c[a][b] *= inv_k;
+  nb_covariance<3>(neighbour, K, 3, c);
 
   float lam[3], f[3][3];  // f[a][j] = component a of eigenvector j
   sym3_eigen(c, lam, f);
@@ -129,8 +105,8 @@ __global__ __launch_bounds__(kLfTile) void local_frames_kernel(const float* __re
     for (int d = 0; d < 3; ++d) xi[d] = pts[(int64_t)i * 3 + d];
     int pos0 = 0, pos2 = 0;
     for (int k = 0; k < K; ++k) {
-      float x[3], dx[3];
-      neighbour(k, x);
+      const NbRow<3> x = neighbour(k);
+      float dx[3];
 #pragma unroll
       for (int d = 0; d < 3; ++d) dx[d] = x[d] - xi[d];
       const float p0 = dx[0] * f[0][0] + dx[1] * f[1][0] + dx[2] * f[2][0];
@@ -156,12 +132,6 @@ __global__ __launch_bounds__(kLfTile) void local_frames_kernel(const float* __re
   for (int a = 0; a < 3; ++a)
 #pragma unroll
     for (int b = 0; b < 3; ++b) of[a * 3 + b] = f[a][b];
-}
-
-__device__ __forceinline__ void cross3(const float (&a)[3], const float (&b)[3], float (&o)[3]) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 __global__ __launch_bounds__(kLfBwdBlock) void local_frames_backward_kernel(
@@ -190,8 +160,8 @@ __global__ __launch_bounds__(kLfBwdBlock) void local_frames_backward_kernel(
   }
   if (disambiguate) {  // y = n x z: g_n += z x g_y, g_z += g_y x n
     float t0[3], t2[3];
-    cross3(v[2], gv[1], t0);
-    cross3(gv[1], v[0], t2);
+    cross3f(v[2], gv[1], t0);
+    cross3f(gv[1], v[0], t2);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       gv[0][a] += t0[a];

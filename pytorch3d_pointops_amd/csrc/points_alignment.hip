@@ -30,18 +30,6 @@
 
 namespace pointops {
 
-// The pivots of cloud n: row 0 of X and of Y (zero for a cloud without rows).
-template <int D>
-__device__ __forceinline__ void pa_pivots(const float* __restrict__ X, const float* __restrict__ Y, int n, int P, int P2,
-                                          int64_t len, double (&px)[D], double (&py)[D]) {
-  const bool hx = len > 0, hy = len > 0 && P2 > 0;
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    px[d] = hx ? (double)X[(int64_t)n * P * D + d] : 0.0;
-    py[d] = hy ? (double)Y[(int64_t)n * P2 * D + d] : 0.0;
-  }
-}
-
 template <int D>
 __global__ __launch_bounds__(kPaBlock) void alignment_moments_kernel(
     const float* __restrict__ X, const float* __restrict__ Y, const int64_t* __restrict__ idx,
@@ -66,28 +54,13 @@ __global__ __launch_bounds__(kPaBlock) void alignment_moments_kernel(
       j = j < 0 ? 0 : (j >= P2 ? P2 - 1 : j);
     }
     const double w = weights != nullptr ? (double)weights[(int64_t)n * P + i] : 1.0;
-    const double w2 = w * w;
     double x[D], y[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       x[d] = (double)xs[i * D + d] - px[d];
       y[d] = (P2 > 0 ? (double)ys[j * D + d] : 0.0) - py[d];
     }
-    acc[S::kSw] += w;
-    acc[S::kSw2] += w2;
-    double xx = 0.0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      acc[S::kSwx + a] += w * x[a];
-      acc[S::kSwy + a] += w * y[a];
-      const double w2x = w2 * x[a];
-      acc[S::kSw2x + a] += w2x;
-      acc[S::kSw2y + a] += w2 * y[a];
-#pragma unroll
-      for (int b = 0; b < D; ++b) acc[S::kSxy + a * D + b] += w2x * y[b];
-      xx += w2x * x[a];
-    }
-    acc[S::kSxx] += xx;
+    pa_accumulate<D>(acc, w, x, y);
   }
   pa_block_sum<M>(acc, s_part, partials + ((int64_t)n * nb + blockIdx.x) * M);
 }
@@ -99,18 +72,10 @@ __global__ __launch_bounds__(kWave) void alignment_solve_kernel(
     float* __restrict__ R, float* __restrict__ T, float* __restrict__ s, double* __restrict__ moments,
     float* __restrict__ sing) {
   constexpr int M = PaSlot<D>::kCount;
-  static_assert(M <= kWave, "one lane per moment");
   __shared__ double s_mom[M];
   const int n = blockIdx.x;
-  if ((int)threadIdx.x < M) {
-    const double* __restrict__ src = partials + (int64_t)n * nb * M + threadIdx.x;
-    double v = 0.0;
-#pragma unroll 8
-    for (int b = 0; b < nb; ++b) v += src[(int64_t)b * M];  // ascending block order: the same sum in every run
-    s_mom[threadIdx.x] = v;
-    if (moments != nullptr) moments[(int64_t)n * M + threadIdx.x] = v;
-  }
-  __syncthreads();
+  pa_sum_partials<M>(partials + (int64_t)n * nb * M, nb, true, s_mom,
+                     moments != nullptr ? moments + (int64_t)n * M : nullptr);
   if (threadIdx.x != 0) return;
   double px[D], py[D], Rd[D][D], Td[D], sd, sg[D];
   pa_pivots<D>(X, Y, n, P, P2, clamped_length<int64_t>(lengths, n, P), px, py);

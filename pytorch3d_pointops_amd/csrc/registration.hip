@@ -114,11 +114,7 @@ __global__ __launch_bounds__(kPaBlock) void registration_moments_kernel(
   const float* __restrict__ ns = EST == kRegPointToPlane ? normals + (int64_t)n * P2 * 3 : nullptr;
   // the pivots: row 0 of the transformed cloud (plane), rows 0 of the original cloud and of the target (point)
   double px[3], py[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    px[d] = len > 0 ? (double)src[d] : 0.0;
-    py[d] = len > 0 ? (double)ys[d] : 0.0;
-  }
+  pa_pivots<3>(EST == kRegPointToPlane ? Xt : X_init, Y, n, P1, P2, len, px, py);
   double acc[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) acc[m] = 0.0;
@@ -152,23 +148,9 @@ __global__ __launch_bounds__(kPaBlock) void registration_moments_kernel(
         acc[kIcpUpper + r] -= J[r] * rho;
       }
     } else {
-      using S = PaSlot<3>;
       const double xc[3] = {x[0] - px[0], x[1] - px[1], x[2] - px[2]};
       const double yc[3] = {q[0] - py[0], q[1] - py[1], q[2] - py[2]};
-      acc[S::kSw] += 1.0;
-      acc[S::kSw2] += 1.0;
-      double xx = 0.0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        acc[S::kSwx + a] += xc[a];
-        acc[S::kSwy + a] += yc[a];
-        acc[S::kSw2x + a] += xc[a];
-        acc[S::kSw2y + a] += yc[a];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) acc[S::kSxy + a * 3 + b] += xc[a] * yc[b];
-        xx += xc[a] * xc[a];
-      }
-      acc[S::kSxx] += xx;
+      pa_accumulate<3>(acc, 1.0, xc, yc);  // weights 1 / 0: every product by 1.0 is exact
     }
   }
   pa_block_sum<M>(acc, s_part, partials + ((int64_t)n * nb + blockIdx.x) * M);
@@ -183,21 +165,11 @@ __global__ __launch_bounds__(kWave) void registration_solve_kernel(
     float* __restrict__ R, float* __restrict__ T, float* __restrict__ fitness, float* __restrict__ inlier_rmse,
     int64_t* __restrict__ num_correspondences, double* __restrict__ moments) {
   constexpr int M = kRegMoments;
-  static_assert(M <= kWave, "one lane per moment");
   __shared__ double s_mom[M];
   const int n = blockIdx.x;
   const bool live = status[n] == kRegRunning;
-  if ((int)threadIdx.x < M) {
-    double v = 0.0;
-    if (live) {
-      const double* __restrict__ src = partials + (int64_t)n * nb * M + threadIdx.x;
-#pragma unroll 8
-      for (int b = 0; b < nb; ++b) v += src[(int64_t)b * M];  // ascending block order: the same sum in every run
-    }
-    s_mom[threadIdx.x] = v;
-    if (moments != nullptr) moments[(int64_t)n * kRegMomentsOut + threadIdx.x] = v;  // (zeros for a frozen cloud)
-  }
-  __syncthreads();
+  pa_sum_partials<M>(partials + (int64_t)n * nb * M, nb, live, s_mom,
+                     moments != nullptr ? moments + (int64_t)n * kRegMomentsOut : nullptr);
   if (threadIdx.x != 0) return;
   double* __restrict__ st = state + (int64_t)n * kRegState;
   double Rd[3][3], Td[3];
@@ -235,6 +207,8 @@ __global__ __launch_bounds__(kWave) void registration_solve_kernel(
         }
       } else if (ok) {
         double px[3], py[3], s, sg[3];
+        // pa_pivots' values (c >= 3: the cloud has rows), read unconditionally: the call costs this kernel 6 VGPRs and a
+        // wave of occupancy
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
           px[d] = (double)X_init[(int64_t)n * P1 * 3 + d];

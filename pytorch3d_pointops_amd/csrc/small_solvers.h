@@ -4,6 +4,9 @@
 //                  rounded to fp32 (local_frames_kernel); sym3_eigen_f64 is its fp64-in, fp64-out core (plane refits).
 //   pa_svd<D>      one-sided Jacobi SVD of a d x d fp64 matrix, U completed by orthogonality where a singular value is
 //                  negligible; pa_solve<D> turns the reduced alignment moments into R, T, s (alignment_solve_kernel).
+//   pa_accumulate  one pair's addends to those moments and pa_pivots<D> the pivots they are taken about
+//                  (alignment_moments_kernel; registration.hip's point-to-point sums with w = 1).
+//   dot3f, cross3f fp32 3-vectors (fpfh.hip, local_frames.hip).
 //
 // They live here so that a host program can run them on millions of matrices without a GPU
 // (tests/native/small_solvers_main.cpp); the kernels include this header and nothing else defines the functions.
@@ -11,6 +14,17 @@
 #include "common.h"
 
 namespace pointops {
+
+// ------------------------------------------------------------------------------------------ fp32 3-vectors
+__host__ __device__ __forceinline__ float dot3f(const float (&a)[3], const float (&b)[3]) {
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+
+__host__ __device__ __forceinline__ void cross3f(const float (&a)[3], const float (&b)[3], float (&o)[3]) {
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
 
 // ------------------------------------------------------------------------------------------ symmetric 3x3 eigensolver
 constexpr int kJacobiMaxSweeps = 12;  // 3x3 cyclic Jacobi converges quadratically: 4-6 sweeps in practice
@@ -108,6 +122,45 @@ struct PaSlot {
   static constexpr int kSw = 0, kSw2 = 1, kSwx = 2, kSwy = 2 + D, kSw2x = 2 + 2 * D, kSw2y = 2 + 3 * D,
                        kSxy = 2 + 4 * D, kSxx = 2 + 4 * D + D * D, kCount = 3 + 4 * D + D * D;
 };
+
+// The pivots of cloud n: row 0 of X and of Y (zero for a cloud without rows).  The moments are sums about them, so that
+// clouds far from the origin lose nothing to cancellation.
+template <int D>
+__host__ __device__ __forceinline__ void pa_pivots(const float* __restrict__ X, const float* __restrict__ Y, int n, int P,
+                                                   int P2, int64_t len, double (&px)[D], double (&py)[D]) {
+  const bool hx = len > 0, hy = len > 0 && P2 > 0;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    px[d] = hx ? (double)X[(int64_t)n * P * D + d] : 0.0;
+    py[d] = hy ? (double)Y[(int64_t)n * P2 * D + d] : 0.0;
+  }
+}
+
+// One pair's addends to the moments acc[PaSlot<D>::kCount]: weight w, x and y about the pivots.  THE statement sequence
+// of the sums (alignment_moments_kernel; registration_moments_kernel's point-to-point branch with w = 1, whose products
+// by 1.0 are exact): reordering it changes result bits.
+template <int D, int M>
+__host__ __device__ __forceinline__ void pa_accumulate(double (&acc)[M], double w, const double (&x)[D],
+                                                       const double (&y)[D]) {
+  using S = PaSlot<D>;
+  static_assert(M >= S::kCount, "the moments are the first slots of acc");
+  const double w2 = w * w;
+  acc[S::kSw] += w;
+  acc[S::kSw2] += w2;
+  double xx = 0.0;
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    acc[S::kSwx + a] += w * x[a];
+    acc[S::kSwy + a] += w * y[a];
+    const double w2x = w2 * x[a];
+    acc[S::kSw2x + a] += w2x;
+    acc[S::kSw2y + a] += w2 * y[a];
+#pragma unroll
+    for (int b = 0; b < D; ++b) acc[S::kSxy + a * D + b] += w2x * y[b];
+    xx += w2x * x[a];
+  }
+  acc[S::kSxx] += xx;
+}
 
 // d x d solve (fp64, one lane).  A = C on entry; on exit A V = U S: columns of A are orthogonal.
 template <int D>

@@ -24,6 +24,7 @@
 //   where sigma_d is negligible AND reflections are allowed: the rebuilt column of U may be the mirror image, which costs
 //   2 sigma_d <= 2e-12 sigma_1 -- measured 2.0e-12 at sigma_d = 1e-12 sigma_1 --; without reflections the determinant
 //   rule picks the right one);  T = py - s px R for zero means.
+// pa_accumulate<2|3>, pa_pivots<2|3> (the addends and pivots of the moment kernels): see run_accumulate.
 // Non-finite entries: every solver returns (the sweep caps), nothing is checked about the values.
 #include <cmath>
 #include <cstdint>
@@ -435,6 +436,67 @@ void run_nonfinite_svd() {
   }
 }
 
+// pa_accumulate over n weighted pairs against the long double sums of the definition, slot by slot, to the bound of
+// the moment tests: n 2^-52 times the sum of the addends' magnitudes (n - 1 additions and at most three roundings per
+// addend, each 2^-53 relative).  pa_pivots: row 0 of each cloud as doubles, zeros for an empty cloud.
+template <int D>
+bool run_accumulate(int n) {
+  using S = pointops::PaSlot<D>;
+  double acc[S::kCount + 2];  // (registration's array is longer than the moments)
+  ld want[S::kCount], mag[S::kCount];
+  for (int m = 0; m < S::kCount + 2; ++m) acc[m] = 0.0;
+  for (int m = 0; m < S::kCount; ++m) want[m] = mag[m] = 0.0L;
+  for (int i = 0; i < n; ++i) {
+    const double w = i % 7 == 0 ? 1.0 : uni();
+    double x[D], y[D];
+    for (int d = 0; d < D; ++d) x[d] = 100.0 * sym(), y[d] = 100.0 * sym();
+    pointops::pa_accumulate<D>(acc, w, x, y);
+    ld t[S::kCount];
+    const ld w2 = (ld)w * w;
+    t[S::kSw] = w;
+    t[S::kSw2] = w2;
+    t[S::kSxx] = 0.0L;
+    for (int a = 0; a < D; ++a) {
+      t[S::kSwx + a] = (ld)w * x[a];
+      t[S::kSwy + a] = (ld)w * y[a];
+      t[S::kSw2x + a] = w2 * x[a];
+      t[S::kSw2y + a] = w2 * y[a];
+      for (int b = 0; b < D; ++b) t[S::kSxy + a * D + b] = w2 * x[a] * y[b];
+      t[S::kSxx] += w2 * x[a] * x[a];
+    }
+    for (int m = 0; m < S::kCount; ++m) want[m] += t[m], mag[m] += fabsl(t[m]);
+  }
+  for (int m = 0; m < S::kCount; ++m) {
+    const ld bound = (ld)n * 2.220446049250313e-16L * mag[m];
+    if (!(fabsl((ld)acc[m] - want[m]) <= bound)) {
+      printf("pa_accumulate<%d>: slot %d is %.17g, the definition gives %.17Lg (bound %.3Le)\n", D, m, acc[m], want[m],
+             bound);
+      return false;
+    }
+  }
+  if (acc[S::kCount] != 0.0 || acc[S::kCount + 1] != 0.0) {
+    printf("pa_accumulate<%d>: wrote past the moments\n", D);
+    return false;
+  }
+  float X[2 * 3 * D], Y[2 * 2 * D];  // two clouds of P = 3 and P2 = 2 rows
+  for (int i = 0; i < 2 * 3 * D; ++i) X[i] = (float)sym();
+  for (int i = 0; i < 2 * 2 * D; ++i) Y[i] = (float)sym();
+  double px[D], py[D];
+  pointops::pa_pivots<D>(X, Y, 1, 3, 2, 3, px, py);
+  for (int d = 0; d < D; ++d)
+    if (px[d] != (double)X[3 * D + d] || py[d] != (double)Y[2 * D + d]) {
+      printf("pa_pivots<%d>: not row 0 of cloud 1\n", D);
+      return false;
+    }
+  pointops::pa_pivots<D>(X, Y, 1, 3, 2, 0, px, py);
+  for (int d = 0; d < D; ++d)
+    if (px[d] != 0.0 || py[d] != 0.0) {
+      printf("pa_pivots<%d>: an empty cloud has pivots\n", D);
+      return false;
+    }
+  return true;
+}
+
 void run_nonfinite_sym3() {
   const float bad[3] = {std::numeric_limits<float>::quiet_NaN(), std::numeric_limits<float>::infinity(),
                         -std::numeric_limits<float>::infinity()};
@@ -460,6 +522,7 @@ int main(int argc, char** argv) {
   if (!run_sym3(per_class)) return 1;
   if (!run_svd<3>(per_class)) return 1;
   if (!run_svd<2>(per_class)) return 1;
+  if (!run_accumulate<3>(per_class) || !run_accumulate<2>(per_class)) return 1;
   run_nonfinite_sym3();
   run_nonfinite_svd<3>();
   run_nonfinite_svd<2>();
