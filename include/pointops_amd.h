@@ -417,8 +417,14 @@ int pointops_icp_iteration(const float* X_init, float* Xt, const float* Y, const
  *      value to every step, since the workspace built by step 0 belongs to one family.  reuse: 0 = build the search structure,
  *      1 = the caller vouches that Y, lengths_y and the shape are those of the previous call into knn_workspace.
  *      d2 = dists[n,r], j = idx[n,r].  (The search runs for the whole batch; a frozen cloud's rows come out unchanged.)
- *   2. Inliers: row r is an inlier iff r < lengths_x[n], lengths_y[n] > 0 and d2 < fl32(max_correspondence_distance *
- *      max_correspondence_distance) -- ball_query's rule.  correspondences[n,r] = j for an inlier, else -1.
+ *      search_version == POINTOPS_REGISTRATION_SEARCH_BOUNDED (no version of knn_points) asks for the BOUNDED search
+ *      instead: the K=1 pointops_knn_in_radius of Xt in Y with radius = max_correspondence_distance, on a
+ *      `knn_workspace` of pointops_knn_in_radius_workspace_bytes(N,P1,P2,3,1) bytes, with the same `reuse`.  Then idx,
+ *      dists hold (-1, 0) on every row with no neighbour inside the radius, and the exact search's values elsewhere.
+ *   2. Inliers: row r is an inlier iff r < lengths_x[n], lengths_y[n] > 0, j >= 0 and d2 < fl32(
+ *      max_correspondence_distance * max_correspondence_distance) -- ball_query's rule (the exact search never gives
+ *      j < 0 where lengths_y[n] > 0; the bounded search gives it exactly where d2 < r2 fails, so both searches give
+ *      the same inliers and every later step the same bytes).  correspondences[n,r] = j for an inlier, else -1.
  *   3. Evaluation: c = the number of inliers, fitness = fl32(c / max(lengths_x[n], 1)) and
  *      inlier_rmse = fl32(sqrt(sum d2 / max(c, 1))) with the sum and the quotients in fp64: they describe the transform
  *      in effect at the search.  num_correspondences[n] = c.
@@ -455,6 +461,7 @@ int pointops_icp_iteration(const float* X_init, float* Xt, const float* Y, const
  * floating-point atomics.  workspace: pointops_registration_workspace_bytes(N, P1).  A short or null workspace of
  * either kind is POINTOPS_EWORKSPACE and nothing is launched.  Nothing synchronises.
  */
+#define POINTOPS_REGISTRATION_SEARCH_BOUNDED (-2)
 int pointops_registration_search_version(void);
 size_t pointops_registration_workspace_bytes(int64_t N, int64_t P1);
 int pointops_registration_step(const float* X_init, const float* Y, const float* target_normals,
@@ -799,6 +806,43 @@ int pointops_statistical_outlier(const float* dists, const int64_t* lengths, int
                                  float std_ratio, float* mean_distance, double* stats, float* threshold, uint8_t* mask,
                                  int64_t* index, int64_t* num_kept, void* workspace, size_t workspace_bytes,
                                  void* stream);
+
+/*
+ * KNN IN RADIUS: the K nearest points among those closer than a radius, sorted by distance -- Open3D's
+ * search_hybrid_vector_3d, PCL's radiusSearch with max_nn on sorted results -- device half of
+ * functions/knn_in_radius.py (csrc/knn_in_radius.hip, radius_knn_kernel.h).  The semantics are this library's own.
+ *   p1 (N,P1,D), p2 (N,P2,D) fp32, D in 1..3; lengths1, lengths2 (N,) or NULL (= P; clamped into [0,P]).
+ *   1. r2 = fl32(radius * radius).  d2(i,j) = ((dx*dx) + dy*dy) + dz*dz over the D coordinates in unfused fp32,
+ *      dx = p1[n,i] - p2[n,j]: ball query's expression, the one pointops_knn_points_idx matches bit for bit.
+ *   2. The CANDIDATES of row i < lengths1[n] are the rows j < lengths2[n] with d2(i,j) < r2 -- ball query's rule.  A
+ *      NaN d2 fails the comparison: such a row is never a neighbour.  d2 == r2 is outside.
+ *   3. The result is the first min(K, #candidates) candidates in ascending (d2, j) order: a tie goes to the lower
+ *      index.  idxs[n,i,k] = j and dists[n,i,k] = d2 for those, then -1 and 0; counts[n,i] = their number.
+ *   4. Rows i >= lengths1[n]: -1, 0, count 0.
+ *   On finite inputs this is pointops_knn_points_idx(K, L2) with every slot whose distance is not below r2, or whose
+ *   position k >= lengths2[n], turned into padding.
+ *   Outputs: idxs (N,P1,K) int64, dists (N,P1,K) fp32; optional (NULL skips it) counts (N,P1) int32.  Every output is
+ *   fully written; the buffers may arrive uninitialised.
+ *   One lane per query.  The target's grid has cells at least 1.001 radius wide; a lane whose 3x3x3 cube is proven to
+ *   contain its ball (every point outside it has a computed d2 >= r2: the face bound of the KNN search) walks the cube,
+ *   any other lane -- no certificate, a grid refused for its cloud (non-finite coordinates, cell caps), a call too
+ *   small for a grid -- scans its cloud in index order with the same comparison.  Both keep the K smallest 64-bit keys
+ *   (d2 bits << 32 | j), whose order is the (d2, j) order (csrc/knn_radius_list.h, host and device code): which path a
+ *   lane takes depends on the input alone and changes no byte.  No atomics on results, nothing synchronises, nothing
+ *   is read back: two calls are byte-equal, a cloud gives the same rows alone and in a batch.
+ *   reuse: 0 = build both sides of the search structure; 1 = the caller vouches that p2, lengths2 and the shape are
+ *   those of the previous call into this workspace, and the radius no larger than that call's (the cells stay wide
+ *   enough; the certificate is taken per call from this call's r2): only the query side is rebuilt.
+ *   workspace: pointops_knn_in_radius_workspace_bytes(N, P1, P2, D, K); a short or null one is POINTOPS_EWORKSPACE with
+ *   nothing launched.  0 <= N < 65536 (a bigger batch goes in slices), 0 <= P1 < 2^30, 0 <= P2 <= the grid KNN's
+ *   largest cloud, 1 <= D <= 3, 1 <= K <= 64, radius finite and > 0, reuse 0 or 1: anything else is POINTOPS_EINVAL
+ *   with nothing launched.  N == 0 and P1 == 0 launch nothing.
+ */
+size_t pointops_knn_in_radius_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K);
+int pointops_knn_in_radius(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2,
+                           int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K, float radius, int64_t* idxs,
+                           float* dists, int32_t* counts, void* workspace, size_t workspace_bytes, int reuse,
+                           void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,8 @@ STATE_WORDS = 16  # fp64 words of a cloud's state: R (9), T (3), prev_fitness, p
 RUNNING, CONVERGED, DEGENERATE = 2, 0, 1  # status of a cloud
 DEGENERATE_PIVOT = 1e-10  # kIcpDegeneratePivot of csrc/icp_plane.h
 MIN_INLIERS = {"point_to_point": 3, "point_to_plane": 6}
+SEARCHES = ("exact", "bounded")
+SEARCH_BOUNDED = -2  # POINTOPS_REGISTRATION_SEARCH_BOUNDED of the header: no version of knn_points
 
 
 class RegistrationState:
@@ -29,7 +31,9 @@ class RegistrationState:
 
     def __init__(self, X_init, Y, normals, lengths_x, lengths_y, R_init, T_init, max_correspondence_distance: float,
                  estimation: str, max_steps: int, relative_fitness: float, relative_rmse: float,
-                 want_moments: bool = False, reuse_grid: bool = True):
+                 want_moments: bool = False, reuse_grid: bool = True, search: str = "exact"):
+        if search not in SEARCHES:
+            raise ValueError(f"registration: search is one of {SEARCHES}, got {search!r}")
         dev = _C._require_gpu(X_init, Y, normals, lengths_x, lengths_y, R_init, T_init)
         self.X_init, self.Y, self.normals = _C._f32c(X_init, "source"), _C._f32c(Y, "target"), \
             _C._f32c(normals, "target_normals")
@@ -75,11 +79,19 @@ class RegistrationState:
         self.moments = out((N, MOMENTS), dtype=torch.float64, device=dev) if want_moments else None
         # asked once per run (-1 unless a debug knob forces the grid) and passed to every step: the search workspace
         # step 0 builds belongs to one kernel family
-        self.search_version = version = _C._lib.pointops_registration_search_version()
-        self.knn_ws, self.knn_ws_bytes = _C._scratch(dev, _C._lib.pointops_knn_workspace_bytes, N, P1, P2, 3, 1,
-                                                     version)
+        # search="bounded": the K = 1 knn_in_radius with the run's radius on a workspace of ITS size; the target side of
+        # its search structure is kept from step 0 on in the same way (a call too small for a grid has none to keep)
+        if search == "bounded":
+            self.search_version = SEARCH_BOUNDED
+            self.knn_ws, self.knn_ws_bytes = _C._scratch(dev, _C._lib.pointops_knn_in_radius_workspace_bytes, N, P1, P2,
+                                                         3, 1)
+            self.uses_grid = True
+        else:
+            self.search_version = version = _C._lib.pointops_registration_search_version()
+            self.knn_ws, self.knn_ws_bytes = _C._scratch(dev, _C._lib.pointops_knn_workspace_bytes, N, P1, P2, 3, 1,
+                                                         version)
+            self.uses_grid = bool(_C._lib.pointops_knn_uses_grid(N, P1, P2, 3, 1, version))
         self.ws, self.ws_bytes = _C._scratch(dev, _C._lib.pointops_registration_workspace_bytes, N, P1)
-        self.uses_grid = bool(_C._lib.pointops_knn_uses_grid(N, P1, P2, 3, 1, version))
         self.reuse_grid = bool(reuse_grid) and self.uses_grid
 
     def step(self, update: bool = True) -> None:

@@ -32,6 +32,7 @@
 //   cluster_grid=0|1   cluster_dbscan: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   iss_grid=0|1       iss_keypoints: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   filter_grid=0|1    remove_radius_outlier: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
+//   knn_in_radius_grid=0|1  knn_in_radius: every lane scans its raw cloud / a grid whenever the shape allows (default: by target size)
 //   registration_grid=1  registration_icp: the step's search through the grid whenever the shape allows (default: by shape)
 //   voxel_long=0|1     voxel_downsample: every voxel summed by one lane / by one wave (default: a wave above 16 members)
 #pragma once

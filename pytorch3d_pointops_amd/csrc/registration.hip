@@ -6,8 +6,10 @@
 // include/pointops_amd.h; in short, per cloud and step:
 //
 //   search    K=1, L2 search of Xt in Y (pointops_knn_points_idx_reuse on the caller's workspace: the grid over the
-//             unmodified target is built once per run) -> idx, d2
-//   inliers   row r counts iff r < len_x, len_y > 0 and d2 < fl32(r_max * r_max)                  (ball_query's rule)
+//             unmodified target is built once per run) -> idx, d2; or, with search_version =
+//             POINTOPS_REGISTRATION_SEARCH_BOUNDED, the K=1 pointops_knn_in_radius with radius r_max: (-1, 0) on the
+//             rows with nothing inside the radius, the same idx, d2 elsewhere
+//   inliers   row r counts iff r < len_x, len_y > 0, idx >= 0 and d2 < fl32(r_max * r_max)        (ball_query's rule)
 //   evaluate  c = inliers, fitness = fl32(c / max(len_x, 1)), inlier_rmse = fl32(sqrt(sum d2 / max(c, 1)))
 //   freeze    status 0 when both moved less than the thresholds since the previous step; else
 //   update    point-to-plane: A = sum J^T J, b = -sum J rho over the inliers about the pivot c0 = Xt[0], one fp64
@@ -125,8 +127,8 @@ __global__ __launch_bounds__(kPaBlock) void registration_moments_kernel(
     float d2 = 0.0f;
     if (i < len && has_y) {
       d2 = d2s[at];
-      in = d2 < r2;
       j = idx[at];
+      in = j >= 0 && d2 < r2;  // (j < 0: the bounded search's "nothing inside the radius")
       j = j < 0 ? 0 : (j >= P2 ? P2 - 1 : j);
     }
     correspondences[at] = in ? j : -1;
@@ -331,10 +333,13 @@ extern "C" int pointops_registration_step(
   const RegistrationLayout l = registration_layout(workspace, N, P1);
   POINTOPS_REQUIRE_WORKSPACE(workspace_fits(workspace, workspace_bytes, l.bytes),
                              "registration_step: workspace of %zu bytes, need %zu", workspace_bytes, l.bytes);
-  POINTOPS_REQUIRE(search_version == -1 || pointops_knn_check_version(search_version, 3, 1),
-                   "registration_step: search_version is -1 or a version of knn_points valid for D = 3, K = 1");
+  const bool bounded = search_version == POINTOPS_REGISTRATION_SEARCH_BOUNDED;
+  POINTOPS_REQUIRE(bounded || search_version == -1 || pointops_knn_check_version(search_version, 3, 1),
+                   "registration_step: search_version is -1, a version of knn_points valid for D = 3, K = 1, or "
+                   "POINTOPS_REGISTRATION_SEARCH_BOUNDED");
   const int version = search_version;
-  const size_t knn_need = pointops_knn_workspace_bytes(N, P1, P2, 3, 1, version);
+  const size_t knn_need = bounded ? pointops_knn_in_radius_workspace_bytes(N, P1, P2, 3, 1)
+                                  : pointops_knn_workspace_bytes(N, P1, P2, 3, 1, version);
   // (before anything is launched)
   POINTOPS_REQUIRE_WORKSPACE(workspace_fits(knn_workspace, knn_workspace_bytes, knn_need),
                              "registration_step: search workspace of %zu bytes, need %zu", knn_workspace_bytes,
@@ -345,8 +350,10 @@ extern "C" int pointops_registration_step(
     hipLaunchKernelGGL(registration_init_kernel, rows, dim3(kPaBlock), 0, stream, X_init, lengths_x, R_init, T_init,
                        (int)P1, Xt, state, status, iterations);
   }
-  int rc = pointops_knn_points_idx_reuse(Xt, Y, lengths_x, lengths_y, N, P1, P2, 3, 2, 1, version, idx, dists,
-                                         knn_workspace, knn_workspace_bytes, reuse, stream_);
+  int rc = bounded ? pointops_knn_in_radius(Xt, Y, lengths_x, lengths_y, N, P1, P2, 3, 1, max_correspondence_distance,
+                                            idx, dists, nullptr, knn_workspace, knn_workspace_bytes, reuse, stream_)
+                   : pointops_knn_points_idx_reuse(Xt, Y, lengths_x, lengths_y, N, P1, P2, 3, 2, 1, version, idx, dists,
+                                                   knn_workspace, knn_workspace_bytes, reuse, stream_);
   if (rc != POINTOPS_OK) return rc;
   const float r2 = max_correspondence_distance * max_correspondence_distance;
   with_exact<kRegPointToPlane>(Ints<kRegPointToPoint>{}, estimation, [&](auto Ec) {

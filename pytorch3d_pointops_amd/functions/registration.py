@@ -70,6 +70,11 @@ def _threshold(value, name):
     return v
 
 
+def _search(value):
+    if value not in _C_registration.SEARCHES:
+        raise ValueError(f"search must be one of {_C_registration.SEARCHES}, got {value!r}")
+
+
 def _transform(transform, N, like, name):
     """(R (N,3,3), T (N,3)) fp32 on the device of `like`, or (None, None): a SimilarityTransform with s == 1 or an
     (R, T) pair."""
@@ -143,6 +148,7 @@ def registration_icp(
     relative_fitness: float = 1e-6,
     relative_rmse: float = 1e-6,
     check_every: int = 1,
+    search: str = "exact",
 ) -> RegistrationResult:
     """Trimmed ICP of every cloud of `source` (N, P1, 3) onto the cloud of `target` (N, P2, 3) with the same batch
     index: float32 CUDA padded tensors (every row valid) or `Pointclouds`.
@@ -173,7 +179,16 @@ def registration_icp(
 
     All sums are float64 in a fixed order: two calls are byte-equal and a cloud gives the same bytes alone and in any
     batch of the same padded widths.  Not differentiable; under torch.compile the call is a graph break.  `target`
-    must not be written while the call runs."""
+    must not be written while the call runs.
+
+    `search="bounded"` replaces the exact search of every step by `knn_in_radius` with K = 1 and radius
+    `max_correspondence_distance`: the pairs a step keeps are inside that radius anyway, so every output is byte-equal
+    to `search="exact"`, and a source row with nothing nearby (clutter, the part of a scan outside the overlap) costs one
+    walk of an empty cube where the exact search scans the whole target for it.  It is not the default because it
+    loses where the radius is large against the point spacing -- the cube of a row holds about 27 rho (1.001 r)^3
+    target rows -- and telling the two cases apart needs the target's extent, which lives on the device: the choice is
+    the caller's."""
+    _search(search)
     max_iterations, check_every = int(max_iterations), int(check_every)
     if max_iterations < 1:
         raise ValueError("max_iterations has to be >= 1.")
@@ -183,7 +198,7 @@ def registration_icp(
     source_clouds, args = _prepare(source, target, max_correspondence_distance, init_transform, "init_transform",
                                    target_normals, estimation)
     with torch.no_grad():
-        state = _C_registration.RegistrationState(*args, max_iterations + 1, *thresholds)
+        state = _C_registration.RegistrationState(*args, max_iterations + 1, *thresholds, search=search)
         stopped = False
         for i in range(max_iterations):
             state.step(update=True)
@@ -203,13 +218,15 @@ def evaluate_registration(
     target: Union[torch.Tensor, Pointclouds],
     max_correspondence_distance: float,
     transform=None,
+    search: str = "exact",
 ) -> RegistrationResult:
     """`fitness`, `inlier_rmse` and the correspondences of `source` under `transform` (default the identity) against
     `target`: exactly the evaluate-only step of `registration_icp`, same arguments, same result type (R, T = the
-    transform in float32, iterations 0, status 2, history of one entry)."""
+    transform in float32, iterations 0, status 2, history of one entry).  `search`: as in `registration_icp`."""
+    _search(search)
     source_clouds, args = _prepare(source, target, max_correspondence_distance, transform, "transform", None,
                                    "point_to_point")
     with torch.no_grad():
-        state = _C_registration.RegistrationState(*args, 1, 0.0, 0.0)
+        state = _C_registration.RegistrationState(*args, 1, 0.0, 0.0, search=search)
         state.step(update=False)
         return _result(state, source_clouds)

@@ -264,12 +264,23 @@ class Pointclouds:
 
         return registration_icp(self, target, max_correspondence_distance, **kwargs)
 
-    def evaluate_registration(self, target, max_correspondence_distance: float, transform=None):
+    def evaluate_registration(self, target, max_correspondence_distance: float, transform=None, search: str = "exact"):
         """The fitness, inlier rmse and correspondences of this batch under `transform` against `target`
         (functions.evaluate_registration)."""
         from ..functions.registration import evaluate_registration
 
-        return evaluate_registration(self, target, max_correspondence_distance, transform)
+        return evaluate_registration(self, target, max_correspondence_distance, transform, search=search)
+
+    def knn_in_radius(self, other: Optional["Pointclouds"] = None, K: int = 1, radius: float = 0.2,
+                      return_nn: bool = False):
+        """KNNInRadius(dists, idx, knn, counts) of every point of this batch: its `K` nearest points of `other` (default:
+        of this batch itself, the point included) among those closer than `radius`, sorted by distance
+        (functions.knn_in_radius): -1 / 0 on the slots beyond them and on padding rows."""
+        from ..functions.knn_in_radius import knn_in_radius
+
+        p1, l1 = self.points_padded(), self.num_points_per_cloud()
+        p2, l2 = (p1, l1) if other is None else (other.points_padded(), other.num_points_per_cloud())
+        return knn_in_radius(p1, p2, l1, l2, K=K, radius=radius, return_nn=return_nn)
 
     def voxel_downsample(self, voxel_size: float, **kwargs) -> "Pointclouds":
         """A new batch with one point per occupied voxel of every cloud -- the centroid of the voxel's points -- and
