@@ -625,6 +625,57 @@ int pointops_iss_keypoints(const float* points, const int64_t* lengths, int64_t 
                            size_t workspace_bytes, void* stream);
 
 /*
+ * Moving-least-squares smoothing (PCL's MovingLeastSquares at polynomial order 1; the plane fit at the core of APSS /
+ * RIMLS): every point is projected onto the plane fitted to its weighted radius neighbourhood, which also yields a
+ * normal and a curvature -- device half of functions/mls.py.  The semantics are this library's own; all fp32 and fp64
+ * arithmetic is unfused and in the order written.  Every output is a function of the input alone: the weighted moments
+ * are summed in integers, so the order of the walk never shows.
+ *   points (N,P,3) fp32; lengths (N,) or NULL (= P; clamped into [0,P]); r = radius.
+ *   d2(i,j) = (dx*dx + dy*dy) + dz*dz in fp32, dx = x_i - x_j: ball query's expression.  r2 = fl32(r * r).  For every
+ *   row i < lengths[n] of cloud n:
+ *   1. SUPPORT.  S_i = { j < lengths[n] : d2(i,j) < r2 }; i itself is in S_i when its coordinates are finite and
+ *      r2 > 0.  num_neighbors[n,i] = |S_i|.
+ *   2. WEIGHT of j in S_i: the compactly supported quartic (1 - d2 / r2)^4 of APSS / RIMLS, in fp32 from the d2 above:
+ *      t = d2 / r2 (one correctly rounded IEEE division), u = 1 - t, w = u * u, w = w * w;  then
+ *      wq = rint((double)w * 2^12), round half to even: an integer in [0, 4096].
+ *   3. INTEGER MOMENTS.  e = the smallest integer with fl32(r) <= 2^e, s = 2^(15 - e) as a double.  Per coordinate
+ *      q = rint(((double)x_j - (double)x_i) * s), round half to even, an integer with |q| < 2^15 + 1.
+ *      W = sum over S_i of wq, M1 = sum of wq q (x, y, z), M2 = sum of wq q q^T (xx, xy, xz, yy, yz, zz), in int64.
+ *      A term is below 2^42 (1 + 2^-13) in magnitude, so with P <= 2^20 no sum reaches 2^63 (csrc/mls_fit.h).
+ *   4. FIT in fp64:  m_a = (double)M1_a / W;  delta_a = m_a / s (the weighted mean offset of the support from x_i);
+ *      C_ab = ((double)M2_ab / W - m_a * m_b) * s^-2.  W == 0: C = 0, delta = 0.  sym3_eigen_f64(C) of
+ *      csrc/small_solvers.h (cyclic Jacobi in fp64) gives the ascending eigenvalues l0 <= l1 <= l2; n is the
+ *      eigenvector of l0, its sign such that its component of largest magnitude is positive (ties to the lower axis).
+ *   5. STATUS (one byte):  1 when num_neighbors < min_neighbors;  else 2 when the support does not determine a plane,
+ *      l1 <= 2^-20 * l2 (a line, a single location, nothing);  else 0.  A row of status 1 or 2 returns its point
+ *      unchanged (the same bits), normal 0 and curvature 0.
+ *   6. OUTPUT of a row of status 0:  normals[n,i,:] = n^ = fl32(n), and the point moves along THAT vector, so that the
+ *      returned point and the returned normal agree to the last bit: in fp64, with n^ widened exactly,
+ *      h = (delta_x n^_x + delta_y n^_y) + delta_z n^_z;  points_out[n,i,a] = fl32((double)x_i,a + h * n^_a), rounded
+ *      once.  (delta has a part along the surface of up to |x_j - x_i|: with the unrounded n the returned normal
+ *      would reproduce the point only to |delta| 2^-24, not to |h| 2^-24.)
+ *      curvature[n,i] = fl32(l0 / ((l0 + l1) + l2)).
+ *   7. ITERATIONS.  The map points -> points_out is applied `iterations` times, each pass on the points the one before
+ *      it wrote (with its own grid, since the points move), alternating between points_out and one workspace buffer;
+ *      normals, curvature, num_neighbors, status and moments are those of the last pass.  All passes are enqueued by
+ *      this one call.  points_out must not overlap points.
+ *   Rows at or past the length: points_out 0, normals 0, curvature 0, num_neighbors 0, status 0 (moments 0).
+ *   Outputs: points_out (N,P,3) fp32, normals (N,P,3) fp32, curvature (N,P) fp32, num_neighbors (N,P) int64, status
+ *   (N,P) one byte per row; optional (NULL skips it) moments (N,P,10) int64 = (W, M1[3], M2[6]).  Every output is fully
+ *   written.  No atomics of its own, nothing synchronises, nothing is read back: results are bit-reproducible, and a
+ *   cloud's rows do not depend on what else is in the batch or on the order of its own rows.
+ *   workspace: pointops_mls_workspace_bytes(N, P, iterations); a short or null one is POINTOPS_EWORKSPACE with nothing
+ *   written.
+ *   0 <= N < 65536 (a bigger batch goes in slices), 0 <= P <= 2^20, radius finite and > 0, min_neighbors >= 0,
+ *   1 <= iterations <= 65536: anything else is POINTOPS_EINVAL with nothing launched.  N == 0 launches nothing.
+ */
+size_t pointops_mls_workspace_bytes(int64_t N, int64_t P, int64_t iterations);
+int pointops_mls_smooth(const float* points, const int64_t* lengths, int64_t N, int64_t P, float radius,
+                        int64_t min_neighbors, int64_t iterations, float* points_out, float* normals, float* curvature,
+                        int64_t* num_neighbors, uint8_t* status, int64_t* moments, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/*
  * RANSAC plane extraction: the dominant plane of every cloud (floor, road, table, wall) -- Open3D's segment_plane,
  * PCL's SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE -- device half of functions/plane.py.  The
  * semantics are this library's own; all fp32 and fp64 arithmetic is unfused and in the order written.  float32 points,

@@ -91,6 +91,8 @@ _SIGNATURES = {
     "pointops_iss_workspace_bytes": (_sz, [_i64, _i64]),
     "pointops_iss_keypoints": (_int, [_vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _sz,
                                       _vp]),
+    "pointops_mls_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "pointops_mls_smooth": (_int, [_vp, _vp, _i64, _i64, _f32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pointops_voxel_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pointops_voxel_downsample": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _sz, _vp]),

@@ -31,6 +31,7 @@
 //   plane_hpl=1|2      segment_plane scoring: hypotheses per lane (default: 2 above 256 hypotheses)
 //   cluster_grid=0|1   cluster_dbscan: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   iss_grid=0|1       iss_keypoints: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
+//   mls_grid=0|1       smooth_mls: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   filter_grid=0|1    remove_radius_outlier: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   knn_in_radius_grid=0|1  knn_in_radius: every lane scans its raw cloud / a grid whenever the shape allows (default: by target size)
 //   registration_grid=1  registration_icp: the step's search through the grid whenever the shape allows (default: by shape)

@@ -233,6 +233,14 @@ class Pointclouds:
 
         return iss_keypoints(self, **kwargs)
 
+    def smooth_mls(self, **kwargs):
+        """MLSSmoothing(points (N, max P_n, 3), normals (N, max P_n, 3), curvature (N, max P_n), num_neighbors, status) of
+        every cloud (functions.smooth_mls, same keywords): every point projected onto the plane fitted to its radius
+        neighbourhood; padding rows are 0."""
+        from ..functions.mls import smooth_mls
+
+        return smooth_mls(self, **kwargs)
+
     def remove_radius_outlier(self, **kwargs):
         """(a new Pointclouds of the points with at least `min_neighbors` others within `radius`, every feature carried
         over; the RadiusOutliers of functions.remove_radius_outlier, same keywords)."""
