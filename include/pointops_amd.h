@@ -895,6 +895,60 @@ int pointops_knn_in_radius(const float* p1, const float* p2, const int64_t* leng
                            float* dists, int32_t* counts, void* workspace, size_t workspace_bytes, int reuse,
                            void* stream);
 
+/*
+ * FEATURE MATCHING: the one or two nearest rows of a descriptor table for every row of another, and the filters that
+ * make putative correspondences of them -- Open3D's correspondences_from_features(mutual_filter), PCL's correspondence
+ * estimation with its rejectors -- device half of functions/match.py (csrc/feature_match.hip, feature_screen.h).
+ *   f1 = p1 (N,P1,D), f2 = p2 (N,P2,D) fp32, 1 <= D < 2^16; lengths1, lengths2 (N,) int64.
+ *   1. (d1, j1) and (d2, j2) are columns 0 and 1 of pointops_knn_points_idx(p1, p2, lengths1, lengths2, norm 2, K = 2):
+ *      squared L2 as the unfused fp32 sum in d order, ties to the lower index.
+ *   2. Row i HAS A NEAREST when i < lengths1[n] and lengths2[n] >= 1; it HAS A SECOND when also lengths2[n] >= 2.
+ *   3. A row is KEPT when it has a nearest and passes every filter that is set:
+ *        max_distance m  d1 < fl32(fl32(m) * fl32(m))   (ball query's comparison)
+ *        ratio rho       d1 < fl32(fl32(rho) * fl32(rho)) * d2 with an fp32 product; rows without a second pass
+ *        mutual          the K = 1 search of p2 over p1 returns i for row j1
+ *   4. corr (N,P1) int64 = j1 where the row is kept, else -1 (what pointops_ransac_alignment takes);
+ *      dists (N,P1) = d1 where the row has a nearest, else 0;  second (N,P1) = d2 where it has a second, +inf where it
+ *      has a nearest only, 0 where it has none;  num_matches (N,) int64 = the rows with corr >= 0.
+ *   Steps 3 and 4 are elementwise and live in functions/match.py; the entry below is step 1.
+ *
+ * pointops_feature_knn: idxs (N,P1,K) int64 and dists (N,P1,K) fp32 in pointops_knn_points_idx's conventions (0 for
+ * rows >= lengths1[n] and slots >= lengths2[n]), byte-equal to that entry on the same inputs on every path; 1 <= K <= 2.
+ *   Two paths.  The EXACT SEARCH is pointops_knn_points_idx itself (version -1).  The SCREEN orders the targets of a
+ *   query by s = fl(fl(n1 + n2) - 2 g) -- norms and dot product as fmaf chains, the dot products on the matrix cores
+ *   (v_mfma_f32_32x32x2_f32, queries on the column side: an accumulator lane owns one query and 16 targets of a 32 x 32
+ *   block) -- keeps the 8 smallest (s, j) per lane, computes the exact distance of the 16 collected targets of a
+ *   query and certifies the row when fl(r_K + E) < s_cut, E = (4 D + 8)(2^-24 (n1 + n2max) + 2^-149) rounded upwards
+ *   (feature_screen.h has the definitions and the proof that then no dropped target can be among the K nearest, ties
+ *   included).  Rows it cannot certify -- a near-tie across the cut, a norm that is not finite or above 2^126 -- go
+ *   into a per-cloud device list and through the exact all-pairs kernel; that launch is always enqueued and ends on
+ *   the device-side count.  Which path a row takes depends on the input alone and changes no byte; no float atomics,
+ *   nothing read back, a fixed launch sequence: two calls are byte-equal and the call can be captured in a HIP graph.
+ *   Dispatch: the screen takes 8 < D <= 128 where it was measured faster than the exact search (profiles/
+ *   match_bench.jsonl): at least 65536 targets and at least 1024 workgroups of 128 queries; every other call is the
+ *   exact search.  POINTOPS_DEBUG=match_screen=0|1 forces the exact search / the screen (any D <= 128).
+ *   stats (N,4) int32, written by the call: 1 if the cloud went through the screen, its rows certified by the screen,
+ *   its rows sent to the exact kernel, 0.
+ *   workspace: pointops_feature_knn_workspace_bytes(N, P1, P2, D, K); a short or null one is POINTOPS_EWORKSPACE with
+ *   nothing launched.  N, P1, P2 >= 0 below 2^31, 1 <= D < 2^16, K in {1, 2}, non-null pointers unless N or P1 is 0: anything
+ *   else is POINTOPS_EINVAL.
+ */
+size_t pointops_feature_knn_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K);
+int pointops_feature_knn(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N,
+                         int64_t P1, int64_t P2, int64_t D, int64_t K, int64_t* idxs, float* dists, int32_t* stats,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Test support, as pointops_knn_grid_stats is: what the screen of pointops_feature_knn computes, from the same tile
+ * code, for small shapes (P1, P2 <= 1024, D <= 128).  s (N,P1,P2): the screen value of every pair with
+ * i < lengths1[n] and j < lengths2[n], 0 elsewhere;  n1 (N,P1), n2 (N,P2): the norms of every row;  n2max (N,): the
+ * largest n2 over j < lengths2[n] (0 for none);  E (N,P1): the bound of every row i < lengths1[n] of a cloud with
+ * lengths2[n] >= 1, 0 elsewhere.
+ */
+int pointops_feature_screen_values(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2,
+                                   int64_t N, int64_t P1, int64_t P2, int64_t D, float* s, float* n1, float* n2,
+                                   float* n2max, float* E, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

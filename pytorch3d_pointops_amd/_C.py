@@ -105,6 +105,9 @@ _SIGNATURES = {
     "pointops_knn_in_radius_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
     "pointops_knn_in_radius": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _sz,
                                       _int, _vp]),
+    "pointops_feature_knn_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "pointops_feature_knn": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pointops_feature_screen_values": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pointops_plane_chunk": (_i64, []),
     "pointops_plane_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pointops_segment_plane": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _int, _f32, _f32, _f32,

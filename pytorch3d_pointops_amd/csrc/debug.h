@@ -35,6 +35,8 @@
 //   filter_grid=0|1    remove_radius_outlier: every cloud by all pairs / a grid whenever the shape allows (default: by cloud size)
 //   knn_in_radius_grid=0|1  knn_in_radius: every lane scans its raw cloud / a grid whenever the shape allows (default: by target size)
 //   registration_grid=1  registration_icp: the step's search through the grid whenever the shape allows (default: by shape)
+//   match_screen=0|1   feature_knn: every call through the exact search / through the MFMA screen whenever the shape allows
+//                      (feature_match.hip; default: by dimension, target count and batch size, where the screen was measured faster)
 //   voxel_long=0|1     voxel_downsample: every voxel summed by one lane / by one wave (default: a wave above 16 members)
 #pragma once
 

@@ -9,6 +9,7 @@ from .fpfh import fpfh_features, mutual_nearest_neighbors, point_pair_features
 from .iss import ISSKeypoints, cloud_resolution, iss_keypoints, keypoints_to_padded
 from .knn import knn_gather, knn_points
 from .knn_in_radius import KNNInRadius, knn_in_radius
+from .match import FeatureMatches, match_features
 from .mls import MLSSmoothing, smooth_mls
 from .packed_to_padded import packed_to_padded, padded_to_packed
 from .points_alignment import (ICPSolution, SimilarityTransform, corresponding_points_alignment,
