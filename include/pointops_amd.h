@@ -949,6 +949,44 @@ int pointops_feature_screen_values(const float* p1, const float* p2, const int64
                                    int64_t N, int64_t P1, int64_t P2, int64_t D, float* s, float* n1, float* n2,
                                    float* n2max, float* E, void* stream);
 
+/*
+ * FEATURE TOP-K: the K nearest rows of a descriptor table for every row of another -- the dynamic graph of DGCNN /
+ * EdgeConv, feature neighbourhoods, candidate lists for learned descriptors -- device half of
+ * functions/knn_features.py (csrc/feature_topk.hip, feature_topk.h, feature_screen.h).
+ *   p1 (N,P1,D), p2 (N,P2,D) fp32, 1 <= D < 2^16; lengths1, lengths2 (N,) int64; 1 <= K, every K that
+ *   pointops_knn_points_idx takes.
+ * pointops_feature_topk: idxs (N,P1,K) int64 and dists (N,P1,K) fp32 EQUAL pointops_knn_points_idx(norm 2, K) byte for
+ * byte on every path: the distance is the unfused fp32 sum in d order, ties go to the lower index, rows >= lengths1[n]
+ * and slots >= lengths2[n] are 0.
+ *   Two paths.  The EXACT SEARCH is pointops_knn_points_idx itself (version -1).  The SCREEN takes D <= 128 and K <= 32
+ *   (the range of the exact all-pairs kernel's register-list instances, which serve as its fallback): it orders the
+ *   targets of a query by s = fl(fl(n1 + n2) - 2 g), the dot products on the matrix cores (v_mfma_f32_32x32x2_f32) as
+ *   in FEATURE MATCHING.  A 256-lane workgroup owns 128 / S queries, S in {1, 4}; target j of a cloud belongs to list
+ *     t(j) = 2 ((j >> 5) mod S) + ((j >> 2) & 1)
+ *   of its query, and each of the 2 S lists keeps the M = 16 smallest (s, j).  The collected targets get the exact
+ *   distance; the lists are merged by (r, j) for the first K; r_K is the K-th distance (+inf if fewer were collected),
+ *   s_cut the smallest 16th key over the lists (+inf for a list that never filled).  The row is CERTIFIED when its norms
+ *   are finite with n1 + n2max <= 2^126 and either lengths2[n] <= 16 or fl(r_K + E) < s_cut,
+ *   E = (4 D + 8)(2^-24 (n1 + n2max) + 2^-149) rounded upwards (feature_topk.h has the proof that then no dropped target
+ *   can be among the K nearest, ties included).  Other rows go into a per-cloud device list and through the exact
+ *   all-pairs kernel; that launch is always enqueued and ends on the device-side count.  K > 16 runs S = 4.  Which path
+ *   a row takes depends on the input alone and changes no byte; no float atomics, nothing read back, a fixed launch
+ *   sequence: two calls are byte-equal and the call can be captured in a HIP graph.
+ *   Dispatch: the screen is the default only where it was measured faster than the exact search (profiles/
+ *   feature_topk_bench.jsonl; csrc/feature_topk.hip states the rule); every other call is the exact search.
+ *   POINTOPS_DEBUG=topk_screen=0|1 forces the exact search / the screen (any D <= 128, K <= 32), topk_split=1|4 forces S
+ *   (K > 16 with S = 1 simply lists more rows).
+ *   stats (N,4) int32, written by the call: 1 if the cloud went through the screen, its rows certified by the screen,
+ *   its rows sent to the exact kernel, the key lists per query (2 S; 0 when not screened).
+ *   workspace: pointops_feature_topk_workspace_bytes(N, P1, P2, D, K); a short or null one is POINTOPS_EWORKSPACE with
+ *   nothing launched.  N, P1, P2 >= 0 below 2^31, 1 <= D < 2^16, K >= 1, non-null pointers unless N or P1 is 0: anything
+ *   else is POINTOPS_EINVAL.
+ */
+size_t pointops_feature_topk_workspace_bytes(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K);
+int pointops_feature_topk(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N,
+                          int64_t P1, int64_t P2, int64_t D, int64_t K, int64_t* idxs, float* dists, int32_t* stats,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

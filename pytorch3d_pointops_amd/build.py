@@ -27,6 +27,9 @@ CXXFLAGS = [
     "-fno-fast-math",
     "-Wall", "-Wno-unused-function",
 ]
+# per source file: no packed fp32 arithmetic (v_pk_*_f32) in the code generated for these
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"feature_topk.hip": NO_PACKED_FP32}
 
 
 def _newest_dep_mtime():
@@ -36,7 +39,7 @@ def _newest_dep_mtime():
 
 
 def _compile(src, obj, verbose):
-    cmd = [HIPCC] + CXXFLAGS + ["-c", src, "-o", obj]
+    cmd = [HIPCC] + CXXFLAGS + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)

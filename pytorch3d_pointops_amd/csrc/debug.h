@@ -37,7 +37,11 @@
 //   registration_grid=1  registration_icp: the step's search through the grid whenever the shape allows (default: by shape)
 //   match_screen=0|1   feature_knn: every call through the exact search / through the MFMA screen whenever the shape allows
 //                      (feature_match.hip; default: by dimension, target count and batch size, where the screen was measured faster)
-//   voxel_long=0|1     voxel_downsample: every voxel summed by one lane / by one wave (default: a wave above 16 members)
+//   topk_screen=0|1    feature_topk: every call through the exact search / through the MFMA screen whenever the shape allows
+//                      (feature_topk.hip: D <= 128 and K <= 32; default: where the screen was measured faster)
+//   topk_split=1|4     feature_topk's screen: 128 / 32 queries per workgroup, 2 / 8 key lists per query (default: 4 for
+//                      K > 16, else by batch size); K > 16 with 1 only lists more rows
+//   voxel_long=0|1    voxel_downsample: every voxel summed by one lane / by one wave (default: a wave above 16 members)
 #pragma once
 
 namespace pointops {

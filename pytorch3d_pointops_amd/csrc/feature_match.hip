@@ -27,6 +27,7 @@
 #include <limits.h>
 
 #include "debug.h"
+#include "feature_match.h"
 #include "feature_screen.h"
 #include "knn_common.h"
 #include "knn_grid.h"
@@ -197,7 +198,8 @@ __global__ __launch_bounds__(256) void feature_screen_kernel(
 
 __global__ __launch_bounds__(256) void feature_stats_kernel(const int64_t* __restrict__ lengths1,
                                                             const int64_t* __restrict__ lengths2, int P1, int P2, int N,
-                                                            const int* __restrict__ qcount, int32_t* __restrict__ stats) {
+                                                            const int* __restrict__ qcount, int lists,
+                                                            int32_t* __restrict__ stats) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const int live = clamped_length<int>(lengths2, n, P2) > 0 ? clamped_length<int>(lengths1, n, P1) : 0;
@@ -205,7 +207,7 @@ __global__ __launch_bounds__(256) void feature_stats_kernel(const int64_t* __res
   stats[4 * n] = qcount != nullptr ? 1 : 0;
   stats[4 * n + 1] = qcount != nullptr ? live - listed : 0;
   stats[4 * n + 2] = listed;
-  stats[4 * n + 3] = 0;
+  stats[4 * n + 3] = qcount != nullptr ? lists : 0;  // (feature_knn: reserved, 0)
 }
 
 static bool match_shape_ok(int64_t N, int64_t P1, int64_t P2, int64_t D, int64_t K) {
@@ -271,11 +273,17 @@ static int launch_screen(const float* p1, const float* p2, const int64_t* l1, co
   return POINTOPS_OK;
 }
 
-static void launch_norms(const float* p1, const float* p2, const int64_t* l2, int64_t N, int64_t P1, int64_t P2, int64_t D,
-                         float* n1, float* n2, unsigned* n2max, hipStream_t stream) {
+void launch_feature_norms(const float* p1, const float* p2, const int64_t* l2, int64_t N, int64_t P1, int64_t P2,
+                          int64_t D, float* n1, float* n2, unsigned* n2max, hipStream_t stream) {
   const int64_t total = N * (P1 + P2);
   hipLaunchKernelGGL(feature_norms_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, stream, p1, p2, l2,
                      (int)P1, (int)P2, (int)D, total, n1, n2, n2max);
+}
+
+void launch_feature_stats(const int64_t* l1, const int64_t* l2, int64_t N, int64_t P1, int64_t P2, const int* qcount,
+                          int lists, int32_t* stats, hipStream_t stream) {
+  hipLaunchKernelGGL(feature_stats_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, stream, l1, l2, (int)P1,
+                     (int)P2, (int)N, qcount, lists, stats);
 }
 
 }  // namespace pointops
@@ -296,8 +304,7 @@ extern "C" int pointops_feature_knn(const float* p1, const float* p2, const int6
   POINTOPS_REQUIRE(lengths1 && lengths2 && stats, "feature_knn: null pointer");
   hipStream_t stream = (hipStream_t)stream_;
   if (P1 == 0) {
-    hipLaunchKernelGGL(feature_stats_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, stream, lengths1, lengths2,
-                       (int)P1, (int)P2, (int)N, (const int*)nullptr, stats);
+    launch_feature_stats(lengths1, lengths2, N, P1, P2, nullptr, 0, stats, stream);
     return check_launch("feature_knn");
   }
   POINTOPS_REQUIRE(p1 && idxs && dists && (p2 || P2 == 0), "feature_knn: null pointer");
@@ -308,12 +315,11 @@ extern "C" int pointops_feature_knn(const float* p1, const float* p2, const int6
     const int rc = pointops_knn_points_idx(p1, p2 ? p2 : p1, lengths1, lengths2, N, P1, P2, D, 2, K, -1, idxs, dists,
                                            l.knn, l.knn_bytes, stream_);
     if (rc != POINTOPS_OK) return rc;
-    hipLaunchKernelGGL(feature_stats_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, stream, lengths1, lengths2,
-                       (int)P1, (int)P2, (int)N, (const int*)nullptr, stats);
+    launch_feature_stats(lengths1, lengths2, N, P1, P2, nullptr, 0, stats, stream);
     return check_launch("feature_knn");
   }
   if (hipMemsetAsync(l.n2max, 0, sizeof(int) * 2 * (size_t)N, stream) != hipSuccess) return check_launch("feature_knn");
-  launch_norms(p1, p2, lengths2, N, P1, P2, D, l.n1, l.n2, l.n2max, stream);
+  launch_feature_norms(p1, p2, lengths2, N, P1, P2, D, l.n1, l.n2, l.n2max, stream);
   int rc = launch_screen(p1, p2, lengths1, lengths2, N, P1, P2, D, K, l.n1, l.n2, l.n2max, l.qlist, l.qcount, idxs,
                          dists, nullptr, nullptr, stream);
   if (rc != POINTOPS_OK) return rc;
@@ -322,8 +328,7 @@ extern "C" int pointops_feature_knn(const float* p1, const float* p2, const int6
   a.qcount = l.qcount;
   rc = launch_knn_wide(a, 2, 1, nullptr);  // the listed rows, whole clouds (no p2 slices: they would write every row)
   if (rc != POINTOPS_OK) return rc;
-  hipLaunchKernelGGL(feature_stats_kernel, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, stream, lengths1, lengths2,
-                     (int)P1, (int)P2, (int)N, (const int*)l.qcount, stats);
+  launch_feature_stats(lengths1, lengths2, N, P1, P2, l.qcount, 0, stats, stream);
   return check_launch("feature_knn");
 }
 
@@ -338,7 +343,7 @@ extern "C" int pointops_feature_screen_values(const float* p1, const float* p2, 
   if (hipMemsetAsync(s, 0, sizeof(float) * (size_t)(N * P1 * P2), stream) != hipSuccess ||
       hipMemsetAsync(n2max, 0, sizeof(float) * (size_t)N, stream) != hipSuccess)
     return check_launch("feature_screen_values");
-  launch_norms(p1, p2, lengths2, N, P1, P2, D, n1, n2, (unsigned*)n2max, stream);
+  launch_feature_norms(p1, p2, lengths2, N, P1, P2, D, n1, n2, (unsigned*)n2max, stream);
   const int rc = launch_screen(p1, p2, lengths1, lengths2, N, P1, P2, D, 1, n1, n2, (const unsigned*)n2max, nullptr,
                                nullptr, nullptr, nullptr, s, E, stream);
   if (rc != POINTOPS_OK) return rc;

@@ -8,6 +8,7 @@ from .filters import (RadiusOutliers, SelectedRows, StatisticalOutliers, mask_to
 from .fpfh import fpfh_features, mutual_nearest_neighbors, point_pair_features
 from .iss import ISSKeypoints, cloud_resolution, iss_keypoints, keypoints_to_padded
 from .knn import knn_gather, knn_points
+from .knn_features import knn_features
 from .knn_in_radius import KNNInRadius, knn_in_radius
 from .match import FeatureMatches, match_features
 from .mls import MLSSmoothing, smooth_mls
