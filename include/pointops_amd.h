@@ -987,6 +987,46 @@ int pointops_feature_topk(const float* p1, const float* p2, const int64_t* lengt
                           int64_t P1, int64_t P2, int64_t D, int64_t K, int64_t* idxs, float* dists, int32_t* stats,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * NEIGHBOUR REDUCE: what the neighbour tables are built for -- the aggregation of EdgeConv / PointNet++ set abstraction
+ * (max, sum, mean over the K neighbours) and the weighted sum of PointNet++ feature propagation (three_interpolate,
+ * knn_interpolate) -- without the (N, L, K, C) tensor of pointops_gather_neighbors; device half of
+ * functions/neighbor_reduce.py (csrc/neighbor_reduce.hip, neighbor_reduce.h, backward_det.h).
+ *   x (N,M,C) fp32, 1 <= C <= 65536; idx (N,L,K) int64; lengths (N,) int64 or NULL; weights (N,L,K) fp32 or NULL;
+ *   reduce: 0 sum, 1 mean, 2 max.  N L K < 2^31 and N M < 2^31 - 1.
+ * A slot (n,l,k) is VALID when 0 <= idx < M and (lengths is NULL or k < lengths[n]): the masks of knn_gather and of
+ * masked_gather together, so every table of the library is taken as it comes (an index >= M, which no search writes, is
+ * padding too and is never followed).
+ *   sum   out[n,l,c] starts at +0.0f; for each valid k in ascending order p = fl(w x[n,idx,c]) (p = x without weights),
+ *         out = fl(out + p).  Unfused, in that order: a function of the inputs alone, two calls are byte-equal.
+ *   mean  the unweighted sum, then one fp32 division by max(count, 1), count = the valid slots of the row.
+ *   max   the value at the first valid slot; a later valid slot replaces it only if v > best (ties: the lowest k).  A row
+ *         without a valid slot gives 0.0f.  arg (N,L,C) uint8: the winning slot, 255 = none; hence K <= 255.
+ *   weights go with sum only; arg is written by max only (NULL otherwise).  out (N,L,C) and arg are fully written, rows of
+ *   padded clouds included.
+ * pointops_neighbor_reduce_backward, from grad_out (N,L,C):
+ *   grad_x (N,M,C), if not NULL: grad_x[n,m,c] = the sum, in ascending (l,k) table order from +0.0f, of fl(f g[n,l,c])
+ *         over the valid entries with idx = m; f = w (weighted sum), fl(1 / max(count,1)) (mean), none (sum, max); max
+ *         counts only the entries with arg[n,l,c] == k.  The table is inverted with the stable sort of the deterministic
+ *         backward passes and every TARGET row pulls its addends: no float atomics, every row written once (0 where
+ *         nothing refers to it).
+ *   grad_w (N,L,K), if not NULL (needs weights and x): sum over c of g[n,l,c] x[n,idx,c] for a valid slot, else 0; the
+ *         order of the additions over c is fixed by C alone (neighbor_reduce.h: per lane ascending, then a fixed tree).
+ *   There is one backward: it is the deterministic one, and the fixed launch sequence can be captured in a HIP graph.
+ *   workspace: pointops_neighbor_reduce_backward_workspace_bytes(N, L, K, M) (0 for sizes the entry refuses); a short or
+ *   null one is POINTOPS_EWORKSPACE with nothing launched.
+ * When C is a multiple of 4 the rows move 16 bytes at a time and x, out, grad_out, grad_x must be 16-byte aligned (arg:
+ * 4-byte).  Anything else named above is POINTOPS_EINVAL, and a rejected call writes nothing.
+ */
+int pointops_neighbor_reduce(const float* x, const int64_t* idx, const int64_t* lengths, const float* weights, int64_t N,
+                             int64_t M, int64_t C, int64_t L, int64_t K, int reduce, float* out, uint8_t* arg,
+                             void* stream);
+size_t pointops_neighbor_reduce_backward_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M);
+int pointops_neighbor_reduce_backward(const float* grad_out, const float* x, const int64_t* idx, const int64_t* lengths,
+                                      const float* weights, const uint8_t* arg, int64_t N, int64_t M, int64_t C,
+                                      int64_t L, int64_t K, int reduce, float* grad_x, float* grad_w, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,19 +13,12 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.h"
+#include "backward_det.h"
 #include "zero_fill.h"
 
 namespace pointops {
 
 constexpr int kDetBlock = 256;
-
-struct DetWs {
-  unsigned *keys_in, *keys_out, *vals_in, *vals_out;
-  int *seg_start, *seg_end;  // per target row (+ the slot of masked entries)
-  void* sort_tmp;
-  size_t sort_tmp_bytes;
-};
 
 static int det_key_bits(int64_t targets) {  // keys 0 .. targets (targets = the slot of masked entries)
   int b = 1;
@@ -34,7 +27,7 @@ static int det_key_bits(int64_t targets) {  // keys 0 .. targets (targets = the 
 }
 
 // the table of N L K entries (at least one) keyed by the N M target rows
-static size_t det_carve(DetWs* ws, void* base, int64_t N, int64_t L, int64_t K, int64_t M) {
+size_t det_carve(DetWs* ws, void* base, int64_t N, int64_t L, int64_t K, int64_t M) {
   const int64_t T = N * L * K > 0 ? N * L * K : 1, targets = N * M;
   Carver c(base);
   DetWs w;
@@ -164,8 +157,8 @@ __global__ __launch_bounds__(kDetBlock) void det_gather_kernel(const float* __re
 }
 
 // keys, stable sort, segments; afterwards ws.vals_out / seg_start / seg_end describe the inverted table
-static int det_invert(const DetWs& ws, const int64_t* idx, const int64_t* lengths1, const int64_t* lengths2, int64_t N,
-                      int64_t L, int64_t K, int64_t M, hipStream_t stream) {
+int det_invert(const DetWs& ws, const int64_t* idx, const int64_t* lengths1, const int64_t* lengths2, int64_t N,
+               int64_t L, int64_t K, int64_t M, hipStream_t stream) {
   const int64_t T = N * L * K, targets = N * M;
   int zrc = zero_words_async(ws.seg_start, targets + 1, stream, "deterministic backward (zero)");
   if (zrc == POINTOPS_OK) zrc = zero_words_async(ws.seg_end, targets + 1, stream, "deterministic backward (zero)");
