@@ -1027,6 +1027,53 @@ int pointops_neighbor_reduce_backward(const float* grad_out, const float* x, con
                                       int64_t L, int64_t K, int reduce, float* grad_x, float* grad_w, void* workspace,
                                       size_t workspace_bytes, void* stream);
 
+/*
+ * NEIGHBOUR ATTENTION: softmax attention of every query row over the K rows its neighbour table names, per head -- the
+ * aggregation of point and graph transformers (TransformerConv on a kNN graph, local self-attention over a kNN table)
+ * -- without the two (N, L, K, C) tensors of pointops_gather_neighbors(k), (v); device half of
+ * functions/neighbor_attention.py (csrc/neighbor_attention.hip, neighbor_attention.h, backward_det.h).
+ *   q (N,L,C), k and v (N,M,C) fp32, C = heads D, D in {4, 8, 16, 32, 64, 128, 256}, C <= 65536; idx (N,L,K) int64;
+ *   lengths (N,) int64 or NULL; bias (N,L,K,heads) fp32 or NULL; scale fp32.  N L K heads < 2^31 and N M < 2^31 - 1.
+ * A slot (n,l,k) is VALID as for NEIGHBOUR REDUCE: 0 <= idx < M and (lengths is NULL or k < lengths[n]).  For row
+ * (n,l) and head h, over the valid slots in ascending k:
+ *   s_k  = fl(fl(scale dot_k) + bias[n,l,k,h])  (no bias: fl(scale dot_k)); dot_k = sum over the D channels of the
+ *          head of q[n,l,h,d] k[n,idx_k,h,d], unfused, in an order fixed by D alone (neighbor_attention.h: the four
+ *          products of a lane ascending, then a fixed tree over the D / 4 lanes of the head).
+ *          A slot COUNTS when it is valid and s_k > -inf: a bias of -inf is weight 0.
+ *   w_k  = exp(s_k - m) / sum_j exp(s_j - m), m = max_k s_k       out[n,l,h,:] = sum_k w_k v[n,idx_k,h,:]
+ *   evaluated in one pass with a running maximum (at most two rescales of the running sum and of the accumulator per
+ *   slot), one fp32 division per channel at the end; exp is expf, documented error 2 units in the last place (2^-23
+ *   relative).  lse[n,l,h] = m + log(sum_k exp(s_k - m)).  A row and head without a counted slot gives out = 0 and
+ *   lse = -inf.  No NaN comes out of finite q, k, v, scale and a bias that is finite or -inf; other non-finite inputs
+ *   are unspecified.  A function of the inputs alone: two calls are byte-equal.  out (N,L,C) and lse (N,L,heads) are
+ *   fully written, rows of padded clouds included.
+ * pointops_neighbor_attention_backward, from grad_out g (N,L,C) and the forward's out and lse:
+ *   p_k = exp(s_k - lse) for a counted slot, else 0 (s_k as the forward computes it);  dP_k = sum_c g[h,c] v[idx_k,h,c];
+ *   delta = sum_c g[h,c] out[h,c];  ds_k = p_k (dP_k - delta)
+ *   grad_bias (N,L,K,heads) = ds_k (0 for a slot that does not count)
+ *   grad_q[n,l,h,:] = scale sum_k ds_k k[idx_k,h,:], in ascending k
+ *   grad_k[n,m,h,:] = scale times the sum, in ascending (l,k) table order from +0.0f, of ds_e q[n,l,h,:] over the valid
+ *         entries e with idx = m;  grad_v[n,m,h,:] = the same sum of p_e g[n,l,h,:].  The table is inverted with the
+ *         stable sort of the deterministic backward passes and every TARGET row pulls its addends: no float atomics,
+ *         every row written once (0 where nothing refers to it).
+ *   Each of grad_q, grad_k, grad_v, grad_bias may be NULL (not wanted); the others are fully written.  There is one
+ *   backward: it is the deterministic one, and the fixed launch sequence can be captured in a HIP graph.
+ *   workspace: pointops_neighbor_attention_backward_workspace_bytes(N, L, K, M, heads) (0 for sizes the entry refuses):
+ *   the inverted table and two (N L K heads) fp32 planes (p and ds); a short or null one is POINTOPS_EWORKSPACE with
+ *   nothing launched.
+ * q, k, v, out, grad_out and the three row gradients move 16 bytes at a time and must be 16-byte aligned.  Anything else
+ * named above is POINTOPS_EINVAL, and a rejected call writes nothing.
+ */
+int pointops_neighbor_attention(const float* q, const float* k, const float* v, const int64_t* idx,
+                                const int64_t* lengths, const float* bias, int64_t N, int64_t L, int64_t M, int64_t K,
+                                int64_t heads, int64_t D, float scale, float* out, float* lse, void* stream);
+size_t pointops_neighbor_attention_backward_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t heads);
+int pointops_neighbor_attention_backward(const float* grad_out, const float* q, const float* k, const float* v,
+                                         const float* out, const float* lse, const int64_t* idx, const int64_t* lengths,
+                                         const float* bias, int64_t N, int64_t L, int64_t M, int64_t K, int64_t heads,
+                                         int64_t D, float scale, float* grad_q, float* grad_k, float* grad_v,
+                                         float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
