@@ -1074,6 +1074,53 @@ int pointops_neighbor_attention_backward(const float* grad_out, const float* q, 
                                          int64_t D, float scale, float* grad_q, float* grad_k, float* grad_v,
                                          float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * NEIGHBOUR CONVOLUTION: the layer point networks put between the searches and the pooling -- a convolution over a
+ * neighbour table with P kernel weights (KPConv: coeff = max(0, 1 - |y_k - x~_p| / sigma); PointConv and continuous
+ * convolutions: coeff from a weight net; with coeff NULL the submanifold sparse convolution whose slot k is kernel
+ * offset k) -- without the (N, L, K, Cin) and (N, L, P, Cin) tensors of pointops_gather_neighbors + einsum + matmul;
+ * device half of functions/neighbor_conv.py (csrc/neighbor_conv.hip, backward_det.h).
+ *   x (N,M,Cin) fp32; idx (N,L,K) int64; lengths (N,) int64 or NULL; coeff (N,L,K,P) fp32 or NULL (then P == K and
+ *   coeff is one-hot: slot k uses weight[k]); weight (P,Cin,Cout) fp32.  Cin and Cout multiples of 4 in [4, 128],
+ *   1 <= P <= 32, 1 <= K <= 255, N L K < 2^31 and N M < 2^31 - 1.
+ * A slot (n,l,k) is VALID as for NEIGHBOUR REDUCE: 0 <= idx < M and (lengths is NULL or k < lengths[n]).
+ *   A[n,l,p,c] starts at +0.0f; for each valid k in ascending order A = fmaf(coeff[n,l,k,p], x[n,idx,c], A).  With
+ *   coeff NULL, A[n,l,p,:] is the row at slot p (added once to +0.0f), or 0 if slot p is invalid.
+ *   out[n,l,o] starts at +0.0f and runs out = fmaf(A[p,c], weight[p,c,o], out) in ascending (p, c): the chain ONE
+ *   accumulator of v_mfma_f32_32x32x2_f32 performs when it is carried across all p (feature_screen.h), so two calls are
+ *   byte-equal and the result does not depend on the tiling.  A row without a valid slot gives 0.  out (N,L,Cout) is
+ *   fully written, rows of padded clouds included.
+ * pointops_neighbor_conv_backward, from grad_out g (N,L,Cout):
+ *   grad_x (N,M,Cin), if not NULL: for target row (n,m), B[p,o] starts at +0.0f and over the valid entries e = (l,k)
+ *         with idx = m, in ascending table order, B = fmaf(coeff[e,p], g[n,l,o], B) (coeff NULL: g[n,l,:] added to
+ *         B[k,:]); then grad_x[n,m,c] = the fmaf chain of B[p,o] weight[p,c,o] in ascending (p, o).  The table is
+ *         inverted with the stable sort of the deterministic backward passes and every TARGET row pulls: no float
+ *         atomics, every row written once (0 where nothing refers to it).
+ *   grad_weight (P,Cin,Cout), if not NULL: grad_weight[p,c,o] = sum over the rows of A[n,l,p,c] g[n,l,o], A as the
+ *         forward computes it: fmaf chains over the rows in ascending order within a chunk of rows, then the chunks'
+ *         partial sums added in ascending chunk order.  The chunks are a function of N L and P alone (tile t of 32 rows
+ *         belongs to chunk t mod min(ceil(N L / 32), max(1, 1024 / P))).
+ *   grad_coeff (N,L,K,P), if not NULL (needs coeff): x[n,idx,:] . T[p,:] for a valid slot, else 0, with T[p,c] the
+ *         fmaf chain of g[n,l,o] weight[p,c,o] in ascending o; the dot is unfused, in an order fixed by Cin alone (the
+ *         four products of a lane ascending, then a fixed tree over the lanes of the row, as NEIGHBOUR REDUCE's grad_w).
+ *   Each gradient may be NULL (not wanted); the others are fully written.  There is one backward: it is the
+ *   deterministic one, and the fixed launch sequence can be captured in a HIP graph.
+ *   workspace: pointops_neighbor_conv_backward_workspace_bytes(N, L, K, M, P, Cin, Cout) (0 for sizes the entry
+ *   refuses): the inverted table and the partial sums of grad_weight; a short or null one is POINTOPS_EWORKSPACE with
+ *   nothing launched.
+ * x and grad_out move 16 bytes at a time and must be 16-byte aligned.  Anything else named above is POINTOPS_EINVAL,
+ * and a rejected call writes nothing.
+ */
+int pointops_neighbor_conv(const float* x, const int64_t* idx, const int64_t* lengths, const float* coeff,
+                           const float* weight, int64_t N, int64_t L, int64_t M, int64_t K, int64_t P, int64_t Cin,
+                           int64_t Cout, float* out, void* stream);
+size_t pointops_neighbor_conv_backward_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t P,
+                                                       int64_t Cin, int64_t Cout);
+int pointops_neighbor_conv_backward(const float* grad_out, const float* x, const int64_t* idx, const int64_t* lengths,
+                                    const float* coeff, const float* weight, int64_t N, int64_t L, int64_t M, int64_t K,
+                                    int64_t P, int64_t Cin, int64_t Cout, float* grad_x, float* grad_weight,
+                                    float* grad_coeff, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

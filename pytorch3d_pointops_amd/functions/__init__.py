@@ -13,6 +13,7 @@ from .knn_in_radius import KNNInRadius, knn_in_radius
 from .match import FeatureMatches, match_features
 from .mls import MLSSmoothing, smooth_mls
 from .neighbor_attention import neighbor_attention
+from .neighbor_conv import neighbor_conv, voxel_neighbors
 from .neighbor_reduce import knn_interpolate, neighbor_reduce
 from .packed_to_padded import packed_to_padded, padded_to_packed
 from .points_alignment import (ICPSolution, SimilarityTransform, corresponding_points_alignment,
