@@ -1121,6 +1121,48 @@ int pointops_neighbor_conv_backward(const float* grad_out, const float* x, const
                                     int64_t P, int64_t Cin, int64_t Cout, float* grad_x, float* grad_weight,
                                     float* grad_coeff, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * NEIGHBOUR CONVOLUTION, 16-bit features (csrc/neighbor_conv16.hip): the same operator for T = bfloat16
+ * (dtype POINTOPS_DTYPE_BF16) or float16 (POINTOPS_DTYPE_F16), the types point networks train in under autocast, on
+ * v_mfma_f32_32x32x16_bf16 / _f16 with fp32 accumulation.
+ *   x (N,M,Cin), weight (P,Cin,Cout), coeff (N,L,K,P) or NULL, out (N,L,Cout) and the gradients are of T, passed as
+ *   void*; idx, lengths and the slot-validity rule are as above.  Cin and Cout multiples of 8 in [8, 256], 1 <= P <= 32,
+ *   1 <= K <= 255, N L K < 2^31 and N M < 2^31 - 1; x and grad_out must be 16-byte aligned.
+ *   A[n,l,p,c]: over the row's valid slots in ascending k, acc = fmaf(float(coeff), float(x), acc) from +0.0f in fp32,
+ *   rounded ONCE to T (to nearest even).  With coeff NULL, A[n,l,k,:] is the row itself (exact), or 0.
+ *   out[n,l,o]: the fp32 matrix-instruction sum over all (p, c) of A weight, ONE accumulator carried across all p,
+ *   rounded once to T.  The order inside a 16-deep step is the hardware's: the promise is that two calls give the same
+ *   bytes, not an fmaf chain.  A row without a valid slot gives 0; out is fully written.
+ * pointops_neighbor_conv16_backward, from grad_out g (N,L,Cout) of T; each gradient is of T, accumulated in fp32 and
+ * rounded once, may be NULL (not wanted), and is otherwise fully written:
+ *   grad_x: for target row (n,m), B[p,o] over the entries of the inverted table in ascending table order, by fmaf in
+ *         fp32 from +0.0f, rounded once to T; then the matrix-instruction sum over (p, o) of B weight[p,c,o].
+ *   grad_weight: A^T g per tile of 32 rows on the matrix instruction (A as the forward rounds it), the tiles of a chunk
+ *         in ascending order in one fp32 accumulator, the chunks' partial sums added in ascending order (the chunks of
+ *         the float32 entry).
+ *   grad_coeff (needs coeff): x[n,idx,:] . T[p,:] for a valid slot, else 0, with T = g weight[p]^T the fp32
+ *         matrix-instruction sum, kept in fp32; the dot is unfused, a lane's eight products ascending, then a fixed tree.
+ *   No float atomics anywhere: there is one backward, it is the deterministic one, and the launch sequences are fixed.
+ *   workspace: pointops_neighbor_conv16_workspace_bytes (the forward: weight repacked in matrix-fragment order, at most
+ *   4 MiB) and pointops_neighbor_conv16_backward_workspace_bytes (the inverted table, the partial sums of grad_weight and
+ *   the transposed pack), both 0 for sizes the entries refuse; a short or null one is POINTOPS_EWORKSPACE with nothing
+ *   launched.  Anything else named above is POINTOPS_EINVAL, and a rejected call writes nothing.
+ */
+#define POINTOPS_DTYPE_BF16 0
+#define POINTOPS_DTYPE_F16 1
+size_t pointops_neighbor_conv16_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t P, int64_t Cin,
+                                                int64_t Cout);
+int pointops_neighbor_conv16(const void* x, const int64_t* idx, const int64_t* lengths, const void* coeff,
+                             const void* weight, int dtype, int64_t N, int64_t L, int64_t M, int64_t K, int64_t P,
+                             int64_t Cin, int64_t Cout, void* out, void* workspace, size_t workspace_bytes,
+                             void* stream);
+size_t pointops_neighbor_conv16_backward_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t P,
+                                                         int64_t Cin, int64_t Cout);
+int pointops_neighbor_conv16_backward(const void* grad_out, const void* x, const int64_t* idx, const int64_t* lengths,
+                                      const void* coeff, const void* weight, int dtype, int64_t N, int64_t L, int64_t M,
+                                      int64_t K, int64_t P, int64_t Cin, int64_t Cout, void* grad_x, void* grad_weight,
+                                      void* grad_coeff, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,9 @@ One autograd node: forward and backward are `_C_neighbor_conv`'s (csrc/neighbor_
 the rows gathered 16 bytes per lane into per-p registers, the product with weight[p] on v_mfma_f32_32x32x2_f32 with one
 accumulator carried across all p; grad_x is the same kernel over the inverted table).  No float atomics, so there is one
 backward and it is the one torch.use_deterministic_algorithms(True) gets.  The definition is the NEIGHBOUR CONVOLUTION
-block of include/pointops_amd.h.
+block of include/pointops_amd.h.  bfloat16 and float16 features take csrc/neighbor_conv16.hip: weight repacked once per call
+in matrix-fragment order, all planes of a chunk through one LDS tile, the product on v_mfma_f32_32x32x16_bf16 / _f16 with
+fp32 accumulation, every result rounded once.
 """
 from typing import Optional
 
@@ -23,6 +25,25 @@ from torch.autograd.function import once_differentiable
 from .. import _C_neighbor_conv
 from ._common import as_f32
 from .neighbor_reduce import _valid_slots
+
+
+class _NeighborConv16Fn(Function):
+    """The node of the bfloat16 / float16 path: every tensor is of x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, idx, weight, lengths, coeff):
+        ctx.save_for_backward(x, idx, weight, lengths, coeff)
+        return _C_neighbor_conv.neighbor_conv16(x, idx, weight, lengths, coeff)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, idx, weight, lengths, coeff = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gx, gw, gc = _C_neighbor_conv.neighbor_conv16_backward(
+            grad_out.to(x.dtype).contiguous(), x, idx, weight, lengths, coeff,
+            need=(need[0], need[2], coeff is not None and need[4]))
+        return gx, None, gw, None, gc
 
 
 class _NeighborConvFn(Function):
@@ -80,9 +101,11 @@ def neighbor_conv(
 
     Differentiable in `x`, `weight` and `coeff`, with one backward that uses no float atomics: two calls give the same
     bytes, also under torch.use_deterministic_algorithms(True).  float32 GPU tensors with Cin and Cout multiples of 4 in
-    [4, 128], P <= 32 and 1 <= K <= 255 take the HIP kernels; CPU tensors, other dtypes and other sizes take the same
-    definition through torch ops (POINTOPS_DEBUG=neighbor_conv=0 forces that route, =1 the kernels).  Under
-    torch.compile the call is a graph break."""
+    [4, 128], P <= 32 and 1 <= K <= 255 take the HIP kernels, and so do GPU tensors whose `x` is bfloat16 or float16 with
+    Cin and Cout multiples of 8 in [8, 256] (`weight` and `coeff` are cast to `x.dtype`; products accumulate in fp32 and
+    every result is rounded once to `x.dtype`); CPU tensors, other dtypes and other sizes take the same definition through
+    torch ops (POINTOPS_DEBUG=neighbor_conv=0 forces that route, =1 the kernels).  Under torch.compile the call is a
+    graph break."""
     if not all(torch.is_tensor(t) for t in (x, idx, weight)) or x.dim() != 3 or idx.dim() != 3 or weight.dim() != 3:
         raise ValueError("x must be of shape (N, M, Cin), idx of shape (N, L, K) and weight of shape (P, Cin, Cout).")
     if idx.shape[0] != x.shape[0] or weight.shape[1] != x.shape[2]:
@@ -100,6 +123,12 @@ def neighbor_conv(
     forced = _C_neighbor_conv.forced()
     native = all(t.is_cuda and t.dtype == torch.float32 for t in tensors) and forced is not False and (
         forced or _C_neighbor_conv.supported(N, L, M, K, P, Cin, Cout))
+    if forced is not False and x.dtype in _C_neighbor_conv.DTYPES16 and all(t.is_cuda for t in tensors) and (
+            forced or _C_neighbor_conv.supported16(N, L, M, K, P, Cin, Cout)):
+        weight, coeff = weight.to(x.dtype), None if coeff is None else coeff.to(x.dtype)  # as _neighbor_conv_torch
+        if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+            return _NeighborConv16Fn.apply(x, idx, weight, lengths, coeff)
+        return _C_neighbor_conv.neighbor_conv16(x, idx, weight, lengths, coeff)  # no node
     if not native:
         return _neighbor_conv_torch(x, idx, weight, lengths, coeff)
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
