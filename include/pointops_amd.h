@@ -1163,6 +1163,56 @@ int pointops_neighbor_conv16_backward(const void* grad_out, const void* x, const
                                       int64_t K, int64_t P, int64_t Cin, int64_t Cout, void* grad_x, void* grad_weight,
                                       void* grad_coeff, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * NEIGHBOUR MLP-MAX: the second layer of a PointNet++ set abstraction or EdgeConv block -- per edge a ReLU, one linear
+ * layer, and the maximum over the K neighbours -- without the two (N, L, K, C) tensors of pointops_gather_neighbors +
+ * add + relu + matmul + amax; device half of functions/neighbor_mlp.py (csrc/neighbor_mlp.hip, backward_det.h).  The
+ * first layer needs no edge-sized work: W1 [f_j, p_j - p_i] + b1 = u[j] + c[i], and this operator starts from u and c.
+ *   x (N,M,C1) fp32 (u); idx (N,L,K) int64; lengths (N,) int64 or NULL; center (N,L,C1) fp32 or NULL (c); weight
+ *   (C1,C2) fp32; bias (C2,) fp32 or NULL.  C1 and C2 multiples of 4 in [4, 128], 1 <= K <= 255, N L K < 2^31 and
+ *   N M < 2^31 - 1.
+ * A slot (n,l,k) is VALID as for NEIGHBOUR REDUCE: 0 <= idx < M and (lengths is NULL or k < lengths[n]).  For a valid
+ * slot k of row (n,l), j = idx[n,l,k]:
+ *   a_i = fl(x[n,j,i] + center[n,l,i]) (no center: x[n,j,i]);  h_i = a_i > 0 ? a_i : +0.0f
+ *   y_c starts at bias[c] (+0.0f without bias) and runs y_c = fmaf(h_i, weight[i,c], y_c) for i ascending: the chain ONE
+ *   accumulator of v_mfma_f32_32x32x2_f32 performs (feature_screen.h).
+ *   best_c is the y_c of the first valid slot; a later valid slot replaces it only if y_c > best_c (ties: the lowest k).
+ *   arg (N,L,C2) uint8: the winning slot, 255 = none; hence K <= 255.
+ *   out[n,l,c] = relu_out ? (best_c > 0 ? best_c : 0) : best_c, applied once after the slots (ReLU and max commute).
+ *   A row without a valid slot gives out = 0 and arg = 255.  A function of the inputs alone: two calls are byte-equal,
+ *   and the result does not depend on the tiling.  out and arg are fully written, rows of padded clouds included.
+ * pointops_neighbor_mlp_max_backward, from grad_out g (N,L,C2) and the forward's out and arg:
+ *   gy[n,l,c] = g if arg != 255 and (!relu_out or out > 0), else 0
+ *   e[n,l,k,i] = the fmaf chain from +0.0f, over c ascending with arg[n,l,c] == k, of gy[c] weight[i,c]
+ *   d = a_i > 0 ? e : 0, a recomputed as above.  Neither e nor d is ever stored.
+ *   grad_center (N,L,C1), if not NULL (needs center): the sum of d over the valid k, ascending from +0.0f.
+ *   grad_x (N,M,C1), if not NULL: the sum of d over the valid entries with idx = m, in ascending (l,k) table order from
+ *         +0.0f.  The table is inverted with the stable sort of the deterministic backward passes and every TARGET row
+ *         pulls: no float atomics, every row written once (0 where nothing refers to it).
+ *   grad_weight (C1,C2), if not NULL: grad_weight[i,c] = sum over the rows of gy[c] h_i(slot arg[c]): fmaf chains over
+ *         the rows b, b + B, b + 2 B, ... of chunk b, then the B partial sums added in ascending b;
+ *         B = min(max(ceil(N L / 32), 1), 1024).  grad_bias (C2,), if not NULL: the same sums of gy[c] (unfused adds).
+ *   Each gradient may be NULL (not wanted); the others are fully written.  There is one backward: it is the
+ *   deterministic one, and the fixed launch sequence can be captured in a HIP graph.
+ *   workspace: pointops_neighbor_mlp_max_backward_workspace_bytes(N, L, K, M, C1, C2) (0 for sizes the entry refuses):
+ *   the inverted table, a transposed copy of weight and the B partial sums -- nothing that grows with K C1 or K C2; a
+ *   short or null one is POINTOPS_EWORKSPACE with nothing launched.
+ * x and center move 16 bytes at a time and must be 16-byte aligned; the forward writes out and arg element by element and
+ * asks nothing of them.  The backward also reads grad_out and out and writes grad_x and grad_center 16 bytes at a time
+ * (16-byte aligned) and reads arg four slots at a time (4-byte aligned).  Anything else named above is POINTOPS_EINVAL,
+ * and a rejected call writes nothing.
+ */
+int pointops_neighbor_mlp_max(const float* x, const int64_t* idx, const int64_t* lengths, const float* center,
+                              const float* weight, const float* bias, int64_t N, int64_t L, int64_t M, int64_t K,
+                              int64_t C1, int64_t C2, int relu_out, float* out, uint8_t* arg, void* stream);
+size_t pointops_neighbor_mlp_max_backward_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t C1,
+                                                          int64_t C2);
+int pointops_neighbor_mlp_max_backward(const float* grad_out, const float* x, const int64_t* idx, const int64_t* lengths,
+                                       const float* center, const float* weight, const float* out, const uint8_t* arg,
+                                       int64_t N, int64_t L, int64_t M, int64_t K, int64_t C1, int64_t C2, int relu_out,
+                                       float* grad_x, float* grad_center, float* grad_weight, float* grad_bias,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ from .match import FeatureMatches, match_features
 from .mls import MLSSmoothing, smooth_mls
 from .neighbor_attention import neighbor_attention
 from .neighbor_conv import neighbor_conv, voxel_neighbors
+from .neighbor_mlp import edge_mlp_max, neighbor_mlp_max
 from .neighbor_reduce import knn_interpolate, neighbor_reduce
 from .packed_to_padded import packed_to_padded, padded_to_packed
 from .points_alignment import (ICPSolution, SimilarityTransform, corresponding_points_alignment,

@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""neighbor_mlp_max on the MI355X against (a) the torch composition of the same definition (`_neighbor_mlp_max_torch`:
+gather, add, relu, matmul, max over K, and its autograd backward), (b) one rocBLAS matmul of (N L K, C1) x (C1, C2)
+alone, the floor of the matrix work, and (c) `neighbor_reduce(max)` on a pre-multiplied x (N, M, C2), the floor of the
+gather.  One JSON line per (shape, C1, C2, pass) into profiles/neighbor_mlp_bench.jsonl (--out).  `--only-new`: the new
+path alone, forward + backward (for a rocprofv3 --kernel-trace --stats run).
+
+The table is uniform random rows of the cloud itself (L = M points, K = 16, full lengths): no locality between the rows
+a query gathers.  The paths run in one process, in alternation, `--rounds` times, each warmed first; times are HIP-event
+times over `steps` consecutive calls (as many as fit in about 50 ms, at most 20); the median is reported with the minimum
+and the maximum.  `fwd` is the forward alone under no_grad, `fwd_bwd` forward + backward to x, center, weight and bias.
+Before anything is timed the outputs of the two paths are compared (1e-4 relative to the largest magnitude), and the
+gradients: the two paths round y differently, so a near-tie may select another slot, and at most a fraction 1e-5 C2 of the
+elements of grad_x and grad_center may differ by more than that (grad_weight and grad_bias: 1e-2 of the largest).
+    flop             2 N L K C1 C2 (the matrix work of the forward)
+    old_error        the composition refused the shape (out of memory, or the launch error of its scatter backward):
+                     that pass is not timed
+    tflops_new       flop over the fused forward time
+    new_over_gemm, new_over_reduce    the fused forward as a multiple of either floor
+    peak_mib_*       torch.cuda.max_memory_allocated over one call, above what was allocated before it
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pytorch3d_pointops_amd.functions import neighbor_mlp_max, neighbor_reduce  # noqa: E402
+from pytorch3d_pointops_amd.functions.neighbor_mlp import _neighbor_mlp_max_torch  # noqa: E402
+
+from bench_neighbor_attention import peak_mib, timed  # noqa: E402
+
+SHAPES = ((8, 65536), (16, 131072), (2, 4096), (32, 1024))
+CONFIGS = ((32, 64), (64, 64), (64, 128), (128, 128))  # C1, C2
+K = 16
+
+
+def bench(N, L, C1, C2, rounds, dev, only_new=False):
+    gen = torch.Generator(device=dev).manual_seed(1000 + N + C1 + C2)
+    x = torch.randn(N, L, C1, generator=gen, device=dev).requires_grad_(True)
+    center = torch.randn(N, L, C1, generator=gen, device=dev).requires_grad_(True)
+    weight = (torch.randn(C1, C2, generator=gen, device=dev) / C1 ** 0.5).requires_grad_(True)
+    bias = torch.randn(C2, generator=gen, device=dev).requires_grad_(True)
+    idx = torch.randint(0, L, (N, L, K), generator=gen, device=dev)
+    up = torch.randn(N, L, C2, generator=gen, device=dev)
+    leaves = [x, center, weight, bias]
+
+    def new():
+        return neighbor_mlp_max(x, idx, weight, bias, center)
+
+    if only_new:
+        for _ in range(3):
+            torch.autograd.grad(new(), leaves, up)
+        torch.cuda.synchronize()
+        return []
+
+    def old():
+        return _neighbor_mlp_max_torch(x, idx, weight, bias, center, None, True)[0]
+
+    old_error = {}
+    try:
+        with torch.no_grad():
+            a, b = new(), old()
+        assert float((a - b).abs().max()) <= 1e-4 * float(b.abs().max()), "forward differs"
+        del a, b
+    except (RuntimeError, torch.OutOfMemoryError) as e:
+        old_error["fwd"] = old_error["fwd_bwd"] = str(e).splitlines()[0]
+    ga = torch.autograd.grad(new(), leaves, up)
+    if not old_error:
+        try:
+            gb = torch.autograd.grad(old(), leaves, up)
+            # (the two paths round y differently, so a near-tie may pick another slot: the top two of K = 16 values of
+            # unit spread lie within a few 1e-6 of each other for a few in 1e6 (row, column) pairs, and one such column
+            # moves the whole row of grad_center and two rows of grad_x: such elements are counted, 1e-5 C2 allowed)
+            worst = max(float(((s - t).abs() > 1e-4 * t.abs().max()).float().mean()) for s, t in zip(ga[:2], gb[:2]))
+            assert worst <= 1e-5 * C2, f"gradient differs in a fraction {worst:.3g} of the elements"
+            worst = max(float((s - t).abs().max()) / float(t.abs().max()) for s, t in zip(ga[2:], gb[2:]))
+            # (sums of N L K signed terms in fp32 on either side: chains of ~1500 roundings of partial sums that are
+            # sqrt(N L) times the result's size, about 2e-3 of it at 2^19 rows; the tests hold the kernels to float64)
+            assert worst <= 1e-2, f"gradient of weight or bias differs: {worst:.3g}"
+            del gb
+        except (RuntimeError, torch.OutOfMemoryError) as e:
+            old_error["fwd_bwd"] = str(e).splitlines()[0]
+    del ga
+    torch.cuda.empty_cache()
+    flop = 2 * N * L * K * C1 * C2
+    rows_out = []
+    for what in ("fwd", "fwd_bwd"):
+        if what == "fwd":
+            def run(fn):
+                with torch.no_grad():
+                    fn()
+        else:
+            def run(fn):
+                torch.autograd.grad(fn(), leaves, up)
+        calls = {"new": lambda: run(new), "old": lambda: run(old)}
+        row = dict(N=N, L=L, K=K, C1=C1, C2=C2, what=what, rounds=rounds, flop=flop)
+        if what in old_error:
+            row["old_error"] = old_error[what]
+            del calls["old"]
+        if what == "fwd":
+            xw = torch.randn(N, L, C2, generator=gen, device=dev)
+            calls["reduce"] = lambda: neighbor_reduce(xw, idx, None, "max")
+            try:
+                A2 = torch.randn(N * L * K, C1, generator=gen, device=dev)
+                W2 = weight.detach()
+                calls["gemm"] = lambda: torch.matmul(A2, W2)
+            except (RuntimeError, torch.OutOfMemoryError) as e:
+                row["gemm_error"] = str(e).splitlines()[0]
+        for name, fn in calls.items():
+            if name in ("new", "old"):
+                row[f"peak_mib_{name}"] = peak_mib(fn)
+        steps = {name: int(min(20, max(1, 50.0 / max(timed(fn, 1), 1e-3)))) for name, fn in calls.items()}  # (warms too)
+        times = {name: [] for name in calls}
+        for _ in range(rounds):  # in alternation: the paths share whatever else the machine is doing
+            for name, fn in calls.items():
+                times[name].append(timed(fn, steps[name]))
+        for name, t in times.items():
+            row[f"ms_{name}"] = round(float(np.median(t)), 4)
+            row[f"ms_min_{name}"] = round(float(np.min(t)), 4)
+            row[f"ms_max_{name}"] = round(float(np.max(t)), 4)
+        if what == "fwd":
+            row["tflops_new"] = round(flop / (row["ms_new"] * 1e-3) / 1e12, 2)
+            row["new_over_reduce"] = round(row["ms_new"] / row["ms_reduce"], 3)
+        if "old" in calls:
+            row["old_over_new"] = round(row["ms_old"] / row["ms_new"], 3)
+        if "gemm" in calls:
+            row["new_over_gemm"] = round(row["ms_new"] / row["ms_gemm"], 3)
+            del A2
+        rows_out.append(row)
+    return rows_out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--configs", default=None, help="indices into CONFIGS, comma-separated")
+    ap.add_argument("--only-new", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--shapes", default=",".join(f"{n}x{p}" for n, p in SHAPES))
+    args = ap.parse_args()
+    if args.rounds < 3:
+        raise SystemExit("at least 3 rounds")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_neighbor_mlp needs a GPU: there is no CPU path to time")
+    dev = torch.device("cuda:0")
+    configs = [CONFIGS[int(i)] for i in args.configs.split(",")] if args.configs else CONFIGS
+    shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
+    if args.only_new:  # nothing is measured: no file is opened
+        for N, L in shapes:
+            for C1, C2 in configs:
+                bench(N, L, C1, C2, args.rounds, dev, only_new=True)
+        return
+    out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                   "neighbor_mlp_bench.jsonl")
+    with open(out, "w") as f:
+        for N, L in shapes:
+            for C1, C2 in configs:
+                for row in bench(N, L, C1, C2, args.rounds, dev):
+                    line = json.dumps(row)
+                    print(line, flush=True)
+                    f.write(line + "\n")
+                    f.flush()
+                torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
