@@ -1213,6 +1213,42 @@ int pointops_neighbor_mlp_max_backward(const float* grad_out, const float* x, co
                                        float* grad_x, float* grad_center, float* grad_weight, float* grad_bias,
                                        void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * NEIGHBOUR MLP-MAX, 16-bit features (csrc/neighbor_mlp16.hip): the same operator for T = bfloat16 (dtype
+ * POINTOPS_DTYPE_BF16) or float16 (POINTOPS_DTYPE_F16) on v_mfma_f32_32x32x16_bf16 / _f16 with fp32 accumulation.
+ *   x, center, weight, bias, grad_out, out and the four gradients are of T, passed as void*; arg is the same uint8 plane;
+ *   idx, lengths and the slot-validity rule are as above.  C1 and C2 multiples of 8 in [8, 256], 1 <= K <= 255,
+ *   N L K < 2^31 and N M < 2^31 - 1.
+ *   a_i = fl32(float(x[n,j,i]) + float(center[n,l,i]));  h_i = rnd_T(a_i > 0 ? a_i : +0): bit for bit what an add and a
+ *   relu in T give.
+ *   y_c is accumulated in fp32 from float(bias[c]) over h_i weight[i,c] by the matrix instruction: inside a 16-deep step
+ *   the order is the hardware's, the steps run ascending, and k positions at or past C1 contribute exact zeros.  The
+ *   promise is that two calls give the same bytes, not an fmaf chain.
+ *   The running maximum and its comparisons are fp32, ties go to the lowest k, and out = rnd_T(act(best)), rounded once.
+ * pointops_neighbor_mlp_max16_backward: gy as above with out > 0 tested on the stored T value; e is an fp32 fmaf chain
+ * over c ascending; d = h_i > 0 ? e : 0 with h recomputed AND ROUNDED as the forward does; the sums of grad_center (over
+ * k) and grad_x (in table order) and the per-chunk partial sums of grad_weight / grad_bias (over h as rounded) are fp32,
+ * each result rounded to T once.  The chunks are B of the float32 entry, capped so that the partial plane holds at most
+ * 1024 * 129 * 128 floats.  No float atomics: there is one backward and it is the deterministic one.
+ *   workspace: pointops_neighbor_mlp_max16_workspace_bytes (the forward: weight transposed and zero-padded to
+ *   (ceil32(C2), ceil16(C1)) of T) and pointops_neighbor_mlp_max16_backward_workspace_bytes (the inverted table, that pack
+ *   and the partial sums; beyond the table nothing depends on K), both 0 for sizes the entries refuse; a short or null
+ *   one is POINTOPS_EWORKSPACE with nothing launched.  x, center, grad_out, out and the row gradients must be 16-byte
+ *   aligned, arg 4-byte.  Anything else named above is POINTOPS_EINVAL, and a rejected call writes nothing.
+ */
+size_t pointops_neighbor_mlp_max16_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t C1, int64_t C2);
+int pointops_neighbor_mlp_max16(const void* x, const int64_t* idx, const int64_t* lengths, const void* center,
+                                const void* weight, const void* bias, int dtype, int64_t N, int64_t L, int64_t M,
+                                int64_t K, int64_t C1, int64_t C2, int relu_out, void* out, uint8_t* arg,
+                                void* workspace, size_t workspace_bytes, void* stream);
+size_t pointops_neighbor_mlp_max16_backward_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t C1,
+                                                            int64_t C2);
+int pointops_neighbor_mlp_max16_backward(const void* grad_out, const void* x, const int64_t* idx, const int64_t* lengths,
+                                         const void* center, const void* weight, const void* out, const uint8_t* arg,
+                                         int dtype, int64_t N, int64_t L, int64_t M, int64_t K, int64_t C1, int64_t C2,
+                                         int relu_out, void* grad_x, void* grad_center, void* grad_weight,
+                                         void* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@
 //   grad_c    per row tile and p, T_p = g_tile weight[p]^T from the transposed pack, kept in fp32 in LDS; the lane groups
 //             dot it with the gathered rows: the lane's eight products ascending, then wave_sum<G>; rounded once.
 // No float atomics; every output element is written once.  Fixed launch sequences, nothing is read back.
+#include "mfma16.h"
 #include "neighbor_conv.h"
 
 namespace pointops {
@@ -43,37 +44,9 @@ constexpr int kNc16GwChannels = 64; // channels of Cin per grad_w workgroup: 32 
 constexpr int kNc16GwStride = kNcRows + kNc16Pad;
 constexpr size_t kNc16LdsMax = (size_t)2 * kNcRows * (512 + kNc16Pad) * 2;  // the 64-row tile at PC Kp = 512
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <class T>
-struct Nc16;
-template <>
-struct Nc16<__bf16> {
-  typedef bf16x8 V;
-  static __device__ __forceinline__ f32x16 mfma(V a, V b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct Nc16<_Float16> {
-  typedef f16x8 V;
-  static __device__ __forceinline__ f32x16 mfma(V a, V b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 constexpr int nc16_pc(int G) { return G >= 32 ? 2 : (G >= 16 ? 4 : 8); }
 constexpr int nc16_rpl(int G) { return G >= 8 ? G / 8 : 1; }  // rows of a 32-row tile a lane works on
 static inline int nc16_up(int64_t v, int to) { return (int)((v + to - 1) / to * to); }
-
-template <class T>
-__device__ __forceinline__ typename Nc16<T>::V nc16_zero() {
-  typename Nc16<T>::V z;
-#pragma unroll
-  for (int x = 0; x < 8; ++x) z[x] = (T)0.0f;
-  return z;
-}
 
 // wp[((p Kp / 8 + kb) Op + o) 8 + j] = w(p, k = 8 kb + j, o) = weight[p Ck Co + k wk + o wo], 0 past Ck or Co
 template <class T>

@@ -27,26 +27,14 @@
 //             row of the winning slot of (row, c); row C1 of the partial is grad_bias.  One partial per chunk in the
 //             workspace, added in ascending chunk order by nm_sum_partials_kernel.
 // Nothing here is sized by K C1 or K C2.  Fixed launch sequences, nothing is read back.
-#include "backward_det.h"
-#include "dispatch.h"
-#include "wave.h"
+#include "neighbor_mlp.h"
 
 namespace pointops {
 
-constexpr int kNmBlock = 256;
-constexpr int kNmWin = 32;                 // slots of a row staged at a time
 constexpr int kNmTileFloats = 128 * 65;    // the LDS tile: 128 rows of C1 <= 64, 64 rows of C1 <= 128
-constexpr int kNmMaxC = 128, kNmMaxK = 255;
-constexpr int kNmMaxChunks = 1024;         // grad_weight / grad_bias: partial sums at the most
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int kNmMaxC = 128;
 
 constexpr int nm_row_tiles(int NB, int KS) { return (4 / NB) * 32 * (2 * KS + 1) <= kNmTileFloats ? 4 / NB : 2 / NB; }
-
-inline int64_t nm_chunks(int64_t rows) {
-  const int64_t c = ceil_div(rows, 32);
-  return c < 1 ? 1 : (c < kNmMaxChunks ? c : kNmMaxChunks);
-}
 
 __device__ __forceinline__ float4 nm_ld4(const float* __restrict__ p) { return *reinterpret_cast<const float4*>(p); }
 
@@ -92,25 +80,7 @@ __global__ __launch_bounds__(kNmBlock) void nm_forward_kernel(
 
   for (int k0 = 0; k0 < K; k0 += kNmWin) {
     const int kt = min(kNmWin, K - k0);
-    __syncthreads();
-    for (int i = t; i < R * kt; i += kNmBlock) {  // one coalesced pass over the table
-      const int r = i / kt, kk = i - r * kt;
-      const int64_t row = row0 + r;
-      int s = -1;
-      if (row < rows) {
-        const int64_t n = row / L, m = idx[row * K + k0 + kk];
-        const int64_t len = lengths == nullptr ? INT64_MAX : lengths[n];
-        if (m >= 0 && m < M && k0 + kk < len) s = (int)(n * M + m);
-      }
-      s_src[kk * R + r] = s;
-    }
-    __syncthreads();
-    for (int i = t; i < kt * RT; i += kNmBlock) {
-      const int kk = i / RT, tile = i - kk * RT;
-      uint32_t m = 0;
-      for (int r = 0; r < 32; ++r) m |= (s_src[kk * R + tile * 32 + r] >= 0 ? 1u : 0u) << r;
-      s_mask[i] = m;
-    }
+    nm_stage<R, RT>(idx, lengths, row0, rows, L, K, M, k0, kt, s_src, s_mask);
 
     float4 v[Q];
     auto gather = [&](int kk) {
@@ -338,21 +308,6 @@ __global__ __launch_bounds__(kNmBlock) void nm_grad_w_kernel(
   }
 }
 
-// the chunks' partial sums in ascending chunk order: rows i < C1 to grad_weight, row C1 to grad_bias (either may be null)
-__global__ __launch_bounds__(256) void nm_sum_partials_kernel(const float* __restrict__ partial, int chunks, int C1,
-                                                              int C2, float* __restrict__ grad_w,
-                                                              float* __restrict__ grad_b) {
-  const int i = blockIdx.x * 256 + threadIdx.x, count = (C1 + 1) * C2;
-  if (i >= count) return;
-  float s = 0.0f;
-  for (int ch = 0; ch < chunks; ++ch) s = s + partial[(int64_t)ch * count + i];
-  if (i < C1 * C2) {
-    if (grad_w != nullptr) grad_w[i] = s;
-  } else if (grad_b != nullptr) {
-    grad_b[i - C1 * C2] = s;
-  }
-}
-
 struct NmWs {
   DetWs det;
   float* wT;       // (C2, C1)
@@ -372,13 +327,7 @@ static size_t nm_carve(NmWs* ws, void* base, int64_t N, int64_t L, int64_t K, in
 }
 
 static bool nm_sizes_ok(int64_t N, int64_t L, int64_t M, int64_t K, int64_t C1, int64_t C2) {
-  return N >= 0 && M >= 0 && L >= 0 && K >= 1 && K <= kNmMaxK && C1 >= 4 && C1 <= kNmMaxC && C1 % 4 == 0 && C2 >= 4 &&
-         C2 <= kNmMaxC && C2 % 4 == 0 && N < (1LL << 31) && M < (1LL << 31) && L < (1LL << 31) &&
-         N * L < (1LL << 31) && N * L * K < (1LL << 31) && N * M < (1LL << 31) - 1;
-}
-
-static bool nm_aligned(const void* a, const void* b, const void* c, const void* d) {
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16) == 0;
+  return nm_index_ok(N, L, M, K) && C1 >= 4 && C1 <= kNmMaxC && C1 % 4 == 0 && C2 >= 4 && C2 <= kNmMaxC && C2 % 4 == 0;
 }
 
 constexpr Ints<1, 2, 4> kNmBlocks{};        // 32-column blocks: the smallest NB >= ceil(C2 / 32)
@@ -472,7 +421,7 @@ extern "C" int pointops_neighbor_mlp_max_backward(const float* grad_out, const f
                            ws.partial);
       });
     });
-    hipLaunchKernelGGL(nm_sum_partials_kernel, dim3((unsigned)ceil_div((C1 + 1) * C2, 256)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(nm_sum_partials_kernel<float>, dim3((unsigned)ceil_div((C1 + 1) * C2, 256)), dim3(256), 0, stream,
                        ws.partial, (int)chunks, (int)C1, (int)C2, grad_weight, grad_bias);
   }
   return check_launch("neighbor_mlp_max_backward");

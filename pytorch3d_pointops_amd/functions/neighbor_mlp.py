@@ -11,7 +11,9 @@ are the M side of a v_mfma_f32_32x32x2_f32 block, weight stays resident in regis
 and its slot are updated elementwise in the accumulator's layout; the backward recomputes the selection from `arg`, so
 nothing edge-sized is saved or written; grad_x is pulled over the inverted table).  No float atomics, so there is one
 backward and it is the one torch.use_deterministic_algorithms(True) gets.  The definition is the NEIGHBOUR MLP-MAX block
-of include/pointops_amd.h.
+of include/pointops_amd.h.  bfloat16 and float16 features take csrc/neighbor_mlp16.hip: weight transposed and zero-padded
+once per call, several slots of a row tile through one LDS tile per barrier pair, the product on
+v_mfma_f32_32x32x16_bf16 / _f16 with fp32 accumulation, every result rounded once.
 """
 from typing import Optional
 
@@ -40,6 +42,28 @@ class _NeighborMlpMaxFn(Function):
         need = ctx.needs_input_grad
         gx, gc, gw, gb = _C_neighbor_mlp.neighbor_mlp_max_backward(
             as_f32(grad_out).contiguous(), x, idx, weight, center, lengths, out, arg, ctx.relu_out,
+            need=(need[0], center is not None and need[4], need[2], need[3]))
+        return gx, None, gw, gb, gc, None, None
+
+
+class _NeighborMlpMax16Fn(Function):
+    """The node of the bfloat16 / float16 path: every tensor is of x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x, idx, weight, bias, center, lengths, relu_out):
+        out, arg = _C_neighbor_mlp.neighbor_mlp_max16(x, idx, weight, bias, center, lengths, relu_out)
+        ctx.save_for_backward(x, center, idx, lengths, weight, out, arg)
+        ctx.relu_out = relu_out
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_arg):
+        x, center, idx, lengths, weight, out, arg = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gx, gc, gw, gb = _C_neighbor_mlp.neighbor_mlp_max16_backward(
+            grad_out.to(x.dtype).contiguous(), x, idx, weight, center, lengths, out, arg, ctx.relu_out,
             need=(need[0], center is not None and need[4], need[2], need[3]))
         return gx, None, gw, gb, gc, None, None
 
@@ -93,9 +117,11 @@ def neighbor_mlp_max(
 
     Differentiable in `x`, `weight`, `bias` and `center`, with one backward that uses no float atomics and holds no
     (N, L, K, .) tensor: two calls give the same bytes, also under torch.use_deterministic_algorithms(True).  float32 GPU
-    tensors with C1 and C2 multiples of 4 in [4, 128] and 1 <= K <= 255 take the HIP kernels; CPU tensors, other dtypes
-    and other sizes take the same definition through torch ops (POINTOPS_DEBUG=neighbor_mlp=0 forces that route, =1
-    the kernels).  Under torch.compile the call is a graph break."""
+    tensors with C1 and C2 multiples of 4 in [4, 128] and 1 <= K <= 255 take the HIP kernels, and so do GPU tensors whose
+    `x` is bfloat16 or float16 with C1 and C2 multiples of 8 in [8, 256] (`weight`, `bias` and `center` are cast to
+    `x.dtype`; the hidden value is rounded to `x.dtype` as a torch add and relu would, products accumulate in fp32 and
+    every result is rounded once); CPU tensors, other dtypes and other sizes take the same definition through torch ops
+    (POINTOPS_DEBUG=neighbor_mlp=0 forces that route, =1 the kernels).  Under torch.compile the call is a graph break."""
     if not all(torch.is_tensor(t) for t in (x, idx, weight)) or x.dim() != 3 or idx.dim() != 3 or weight.dim() != 2:
         raise ValueError("x must be of shape (N, M, C1), idx of shape (N, L, K) and weight of shape (C1, C2).")
     if idx.shape[0] != x.shape[0] or weight.shape[0] != x.shape[2]:
@@ -114,7 +140,14 @@ def neighbor_mlp_max(
     forced = _C_neighbor_mlp.forced()
     native = all(t.is_cuda and t.dtype == torch.float32 for t in tensors) and forced is not False and (
         forced or _C_neighbor_mlp.supported(N, L, M, K, C1, C2))
-    if not native:
+    if forced is not False and x.dtype in _C_neighbor_mlp.DTYPES16 and all(t.is_cuda for t in tensors) and (
+            forced or _C_neighbor_mlp.supported16(N, L, M, K, C1, C2)):
+        weight, bias, center = (None if t is None else t.to(x.dtype) for t in (weight, bias, center))  # as the torch route
+        if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+            out, arg = _NeighborMlpMax16Fn.apply(x, idx, weight, bias, center, lengths, relu_out)
+        else:
+            out, arg = _C_neighbor_mlp.neighbor_mlp_max16(x, idx, weight, bias, center, lengths, relu_out)  # no node
+    elif not native:
         out, arg = _neighbor_mlp_max_torch(x, idx, weight, bias, center, lengths, relu_out)
     elif torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         out, arg = _NeighborMlpMaxFn.apply(x, idx, weight, bias, center, lengths, relu_out)

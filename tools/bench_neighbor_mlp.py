@@ -18,6 +18,11 @@ elements of grad_x and grad_center may differ by more than that (grad_weight and
     tflops_new       flop over the fused forward time
     new_over_gemm, new_over_reduce    the fused forward as a multiple of either floor
     peak_mib_*       torch.cuda.max_memory_allocated over one call, above what was allocated before it
+`--dtype bfloat16|float16` times csrc/neighbor_mlp16.hip instead (into profiles/neighbor_mlp16_bench.jsonl): `old` is then
+the composition in that dtype (the route these inputs took before the 16-bit kernels), `f32` the float32 kernels on the
+same values, `gemm` one matmul in that dtype, and there is no `reduce`.  Before anything is timed the forward is compared
+with the float32 kernels' and the composition's (2^-5 relative to the largest magnitude: h and out are rounded to the type); the gradients are
+the tests' business.
 """
 import argparse
 import json
@@ -38,15 +43,17 @@ CONFIGS = ((32, 64), (64, 64), (64, 128), (128, 128))  # C1, C2
 K = 16
 
 
-def bench(N, L, C1, C2, rounds, dev, only_new=False):
+def bench(N, L, C1, C2, rounds, dev, only_new=False, dtype=torch.float32):
     gen = torch.Generator(device=dev).manual_seed(1000 + N + C1 + C2)
-    x = torch.randn(N, L, C1, generator=gen, device=dev).requires_grad_(True)
-    center = torch.randn(N, L, C1, generator=gen, device=dev).requires_grad_(True)
-    weight = (torch.randn(C1, C2, generator=gen, device=dev) / C1 ** 0.5).requires_grad_(True)
-    bias = torch.randn(C2, generator=gen, device=dev).requires_grad_(True)
+    half = dtype != torch.float32
+    x = torch.randn(N, L, C1, generator=gen, device=dev).to(dtype).requires_grad_(True)
+    center = torch.randn(N, L, C1, generator=gen, device=dev).to(dtype).requires_grad_(True)
+    weight = (torch.randn(C1, C2, generator=gen, device=dev) / C1 ** 0.5).to(dtype).requires_grad_(True)
+    bias = torch.randn(C2, generator=gen, device=dev).to(dtype).requires_grad_(True)
     idx = torch.randint(0, L, (N, L, K), generator=gen, device=dev)
-    up = torch.randn(N, L, C2, generator=gen, device=dev)
+    up = torch.randn(N, L, C2, generator=gen, device=dev).to(dtype)
     leaves = [x, center, weight, bias]
+    leaves32 = [t.detach().float().requires_grad_(True) for t in leaves] if half else None
 
     def new():
         return neighbor_mlp_max(x, idx, weight, bias, center)
@@ -60,16 +67,29 @@ def bench(N, L, C1, C2, rounds, dev, only_new=False):
     def old():
         return _neighbor_mlp_max_torch(x, idx, weight, bias, center, None, True)[0]
 
+    def f32():
+        return neighbor_mlp_max(leaves32[0], idx, leaves32[2], leaves32[3], leaves32[1])
+
     old_error = {}
+    if half:
+        with torch.no_grad():
+            a, b = new().float(), f32()
+        assert float((a - b).abs().max()) <= 2.0 ** -5 * float(b.abs().max()), "forward differs from the float32 kernels"
+        del a, b
     try:
         with torch.no_grad():
-            a, b = new(), old()
-        assert float((a - b).abs().max()) <= 1e-4 * float(b.abs().max()), "forward differs"
+            a, b = new().float(), old().float()
+        assert float((a - b).abs().max()) <= (2.0 ** -5 if half else 1e-4) * float(b.abs().max()), "forward differs"
         del a, b
     except (RuntimeError, torch.OutOfMemoryError) as e:
         old_error["fwd"] = old_error["fwd_bwd"] = str(e).splitlines()[0]
     ga = torch.autograd.grad(new(), leaves, up)
-    if not old_error:
+    if half and not old_error:
+        try:
+            torch.autograd.grad(old(), leaves, up)
+        except (RuntimeError, torch.OutOfMemoryError) as e:
+            old_error["fwd_bwd"] = str(e).splitlines()[0]
+    elif not old_error:
         try:
             gb = torch.autograd.grad(old(), leaves, up)
             # (the two paths round y differently, so a near-tie may pick another slot: the top two of K = 16 values of
@@ -95,23 +115,27 @@ def bench(N, L, C1, C2, rounds, dev, only_new=False):
                     fn()
         else:
             def run(fn):
-                torch.autograd.grad(fn(), leaves, up)
+                torch.autograd.grad(fn(), leaves32 if fn is f32 else leaves, up.float() if fn is f32 else up)
         calls = {"new": lambda: run(new), "old": lambda: run(old)}
-        row = dict(N=N, L=L, K=K, C1=C1, C2=C2, what=what, rounds=rounds, flop=flop)
+        if half:
+            calls["f32"] = lambda: run(f32)
+        row = dict(N=N, L=L, K=K, C1=C1, C2=C2, what=what, rounds=rounds, flop=flop,
+                   dtype=str(dtype).replace("torch.", ""))
         if what in old_error:
             row["old_error"] = old_error[what]
             del calls["old"]
         if what == "fwd":
-            xw = torch.randn(N, L, C2, generator=gen, device=dev)
-            calls["reduce"] = lambda: neighbor_reduce(xw, idx, None, "max")
+            if not half:
+                xw = torch.randn(N, L, C2, generator=gen, device=dev)
+                calls["reduce"] = lambda: neighbor_reduce(xw, idx, None, "max")
             try:
-                A2 = torch.randn(N * L * K, C1, generator=gen, device=dev)
+                A2 = torch.randn(N * L * K, C1, generator=gen, device=dev).to(dtype)
                 W2 = weight.detach()
                 calls["gemm"] = lambda: torch.matmul(A2, W2)
             except (RuntimeError, torch.OutOfMemoryError) as e:
                 row["gemm_error"] = str(e).splitlines()[0]
         for name, fn in calls.items():
-            if name in ("new", "old"):
+            if name in ("new", "old", "f32"):
                 row[f"peak_mib_{name}"] = peak_mib(fn)
         steps = {name: int(min(20, max(1, 50.0 / max(timed(fn, 1), 1e-3)))) for name, fn in calls.items()}  # (warms too)
         times = {name: [] for name in calls}
@@ -124,9 +148,12 @@ def bench(N, L, C1, C2, rounds, dev, only_new=False):
             row[f"ms_max_{name}"] = round(float(np.max(t)), 4)
         if what == "fwd":
             row["tflops_new"] = round(flop / (row["ms_new"] * 1e-3) / 1e12, 2)
-            row["new_over_reduce"] = round(row["ms_new"] / row["ms_reduce"], 3)
+            if "reduce" in calls:
+                row["new_over_reduce"] = round(row["ms_new"] / row["ms_reduce"], 3)
         if "old" in calls:
             row["old_over_new"] = round(row["ms_old"] / row["ms_new"], 3)
+        if "f32" in calls:
+            row["f32_over_new"] = round(row["ms_f32"] / row["ms_new"], 3)
         if "gemm" in calls:
             row["new_over_gemm"] = round(row["ms_new"] / row["ms_gemm"], 3)
             del A2
@@ -141,25 +168,28 @@ def main():
     ap.add_argument("--only-new", action="store_true")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shapes", default=",".join(f"{n}x{p}" for n, p in SHAPES))
+    ap.add_argument("--dtype", default="float32", choices=("float32", "bfloat16", "float16"))
     args = ap.parse_args()
     if args.rounds < 3:
         raise SystemExit("at least 3 rounds")
     if not torch.cuda.is_available():
         raise SystemExit("bench_neighbor_mlp needs a GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
-    configs = [CONFIGS[int(i)] for i in args.configs.split(",")] if args.configs else CONFIGS
+    dtype = getattr(torch, args.dtype)
+    all_configs = CONFIGS if dtype == torch.float32 else CONFIGS + ((256, 256),)  # (the 16-bit kernels go to 256)
+    configs = [all_configs[int(i)] for i in args.configs.split(",")] if args.configs else all_configs
     shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
     if args.only_new:  # nothing is measured: no file is opened
         for N, L in shapes:
             for C1, C2 in configs:
-                bench(N, L, C1, C2, args.rounds, dev, only_new=True)
+                bench(N, L, C1, C2, args.rounds, dev, only_new=True, dtype=dtype)
         return
     out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                   "neighbor_mlp_bench.jsonl")
+                                   "neighbor_mlp_bench.jsonl" if dtype == torch.float32 else "neighbor_mlp16_bench.jsonl")
     with open(out, "w") as f:
         for N, L in shapes:
             for C1, C2 in configs:
-                for row in bench(N, L, C1, C2, args.rounds, dev):
+                for row in bench(N, L, C1, C2, args.rounds, dev, dtype=dtype):
                     line = json.dumps(row)
                     print(line, flush=True)
                     f.write(line + "\n")
