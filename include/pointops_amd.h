@@ -1249,6 +1249,58 @@ int pointops_neighbor_mlp_max16_backward(const void* grad_out, const void* x, co
                                          int relu_out, void* grad_x, void* grad_center, void* grad_weight,
                                          void* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * NEIGHBOUR MLP-MAX, two layers on 16-bit features (csrc/neighbor_mlp2_16.hip): one more hidden layer between the inner
+ * ReLU and the layer that is max-pooled, for T = bfloat16 or float16 (dtype as above), so that a three-layer block of
+ * PointNet++ or a two-layer EdgeConv needs no edge-sized tensor.
+ *   x (N,M,C1), center (N,L,C1) or NULL, weight (C1,C2), bias (C2,) or NULL, weight2 (C2,C3), bias2 (C3,) or NULL, grad_out
+ *   and out (N,L,C3) and the six gradients are of T, passed as void*; arg (N,L,C3) uint8.  C1 and C2 multiples of 8 in
+ *   [8, 128], C3 a multiple of 8 in [8, 256], 1 <= K <= 255, N L K < 2^31 and N M < 2^31 - 1.  Slot validity is as above.
+ *   h1_i = rnd_T(relu(fl32(float(x[n,j,i]) + float(center[n,l,i])))), as the one-layer entry forms h.
+ *   h2_c = rnd_T(relu(z_c)), z_c accumulated in fp32 from float(bias[c]) over h1_i weight[i,c] by the matrix instruction
+ *   (steps ascending, k positions at or past C1 exact zeros): ONE rounding to T, what a matmul + add + relu in T gives up
+ *   to the order of the fp32 sum.
+ *   y_d is accumulated in fp32 from float(bias2[d]) over h2_c weight2[c,d] likewise; the running maximum, its ties (the
+ *   lowest k), arg, the empty row (0 and 255) and out = rnd_T(act(best)) are as above.  Two calls give the same bytes.
+ * pointops_neighbor_mlp2_max16_backward, from grad_out g (N,L,C3) and the forward's out and arg; h1 and h2 are recomputed
+ * AND ROUNDED as the forward does, nothing edge-sized is read from the caller:
+ *   gy as above (out > 0 tested on the stored T value);  e3[k,d] = gy[d] if arg[d] == k else 0, a value of T (exact)
+ *   e2[k,c] = h2_c > 0 ? fp32acc(e3[k,:] . weight2[c,:]) : 0 (fp32); as a matrix operand it is ROUNDED to T; the
+ *         products below also take what that rounding dropped, itself rounded to T, as a second operand (e2 to about 16
+ *         bits), and so does h2 in grad_weight2, whose reference value is the unrounded relu.
+ *   e1[k,i] = h1_i > 0 ? fp32acc(e2[k,:] . weight[i,:]) : 0                (fp32)
+ *   grad_center (N,L,C1) = rnd_T( sum over k ascending of e1 in fp32 )                           roundings: e2, result
+ *   grad_x (N,M,C1) = rnd_T( sum in table order, fp32, of rnd_T(e1) )     -- e1 passes through a workspace of T
+ *                                                                                    roundings: e2, e1, result
+ *   grad_weight (C1,C2) = rnd_T( sum over all pairs of h1_i e2_c )                              roundings: e2, result
+ *   grad_bias (C2,) = rnd_T( sum of the fp32 e2_c )                                             roundings: result
+ *   grad_weight2 (C2,C3) = rnd_T( sum over all pairs of h2_c e3_d )                             roundings: h2, result
+ *   grad_bias2 (C3,) = rnd_T( sum of gy_d )                                                     roundings: result
+ *   The weight and bias sums are fp32 matrix-instruction accumulations per workgroup (at most 256 workgroups, each over
+ *   the row tiles b, b + B, ...; for C1 or C2 <= 64 split further over the pair index), the partial sums then added in
+ *   ascending order.  Each gradient may be NULL.  No float atomics: there is one backward, the deterministic one.
+ *   workspace: pointops_neighbor_mlp2_max16_workspace_bytes (both weights in fragment order) and
+ *   pointops_neighbor_mlp2_max16_backward_workspace_bytes (the inverted table, three packs, the partial sums, and e1
+ *   (N,L,K,C1) of T, which lives only inside the call), both 0 for sizes the entries refuse; a short or null one is
+ *   POINTOPS_EWORKSPACE with nothing launched.  x, center, grad_out, out and grad_x must be 16-byte aligned, arg 4-byte.
+ *   Anything else named above is POINTOPS_EINVAL, and a rejected call writes nothing.
+ */
+size_t pointops_neighbor_mlp2_max16_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t C1, int64_t C2,
+                                                    int64_t C3);
+int pointops_neighbor_mlp2_max16(const void* x, const int64_t* idx, const int64_t* lengths, const void* center,
+                                 const void* weight, const void* bias, const void* weight2, const void* bias2, int dtype,
+                                 int64_t N, int64_t L, int64_t M, int64_t K, int64_t C1, int64_t C2, int64_t C3,
+                                 int relu_out, void* out, uint8_t* arg, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+size_t pointops_neighbor_mlp2_max16_backward_workspace_bytes(int64_t N, int64_t L, int64_t K, int64_t M, int64_t C1,
+                                                             int64_t C2, int64_t C3);
+int pointops_neighbor_mlp2_max16_backward(const void* grad_out, const void* x, const int64_t* idx, const int64_t* lengths,
+                                          const void* center, const void* weight, const void* bias, const void* weight2,
+                                          const void* out, const uint8_t* arg, int dtype, int64_t N, int64_t L, int64_t M,
+                                          int64_t K, int64_t C1, int64_t C2, int64_t C3, int relu_out, void* grad_x,
+                                          void* grad_center, void* grad_weight, void* grad_bias, void* grad_weight2,
+                                          void* grad_bias2, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,13 @@ _SIGNATURES = {
     "pointops_neighbor_mlp_max16_backward_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "pointops_neighbor_mlp_max16_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64,
                                                     _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pointops_neighbor_mlp2_max16_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "pointops_neighbor_mlp2_max16": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64,
+                                            _i64, _i64, _int, _vp, _vp, _vp, _sz, _vp]),
+    "pointops_neighbor_mlp2_max16_backward_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "pointops_neighbor_mlp2_max16_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64,
+                                                     _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     _vp, _sz, _vp]),
     "pointops_plane_chunk": (_i64, []),
     "pointops_plane_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "pointops_segment_plane": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _int, _f32, _f32, _f32,

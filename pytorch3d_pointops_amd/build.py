@@ -32,7 +32,7 @@ NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"feature_topk.hip": NO_PACKED_FP32, "neighbor_reduce.hip": NO_PACKED_FP32,
                "neighbor_attention.hip": NO_PACKED_FP32, "neighbor_conv.hip": NO_PACKED_FP32,
                "neighbor_conv16.hip": NO_PACKED_FP32, "neighbor_mlp.hip": NO_PACKED_FP32,
-               "neighbor_mlp16.hip": NO_PACKED_FP32}
+               "neighbor_mlp16.hip": NO_PACKED_FP32, "neighbor_mlp2_16.hip": NO_PACKED_FP32}
 
 
 def _newest_dep_mtime():

@@ -161,8 +161,95 @@ def bench(N, L, C1, C2, rounds, dev, only_new=False, dtype=torch.float32):
     return rows_out
 
 
+CONFIGS2 = ((64, 64, 128), (128, 128, 256), (64, 64, 64))  # C1, C2, C3
+
+
+def bench2(N, L, C1, C2, C3, rounds, dev, only_new, dtype):
+    """--layers 2: `new` the fused two-layer path, `old` the torch composition in the same dtype, `parent` the best route
+    without weight2 (torch ops up to the hidden pre-activation as an (N, L K, C2) tensor, then neighbor_mlp_max over an
+    identity table), `gemm` the two matmuls of the edge matrix.  flop = 2 N L K (C1 C2 + C2 C3)."""
+    gen = torch.Generator(device=dev).manual_seed(2000 + N + C1 + C3)
+    rnd = lambda *s, scale=1.0: (torch.randn(*s, generator=gen, device=dev) * scale).to(dtype).requires_grad_(True)  # noqa: E731
+    x, center, weight, bias = rnd(N, L, C1), rnd(N, L, C1), rnd(C1, C2, scale=C1 ** -0.5), rnd(C2)
+    weight2, bias2 = rnd(C2, C3, scale=C2 ** -0.5), rnd(C3)
+    idx = torch.randint(0, L, (N, L, K), generator=gen, device=dev)
+    own = torch.arange(L * K, device=dev).reshape(1, L, K).expand(N, L, K).contiguous()
+    up = torch.randn(N, L, C3, generator=gen, device=dev).to(dtype)
+    leaves = [x, center, weight, bias, weight2, bias2]
+
+    def new():
+        return neighbor_mlp_max(x, idx, weight, bias, center, weight2=weight2, bias2=bias2)
+
+    def old():
+        return _neighbor_mlp_max_torch(x, idx, weight, bias, center, None, True, weight2, bias2)[0]
+
+    def parent():
+        a = x.gather(1, idx.reshape(N, L * K, 1).expand(-1, -1, C1)).reshape(N, L, K, C1) + center[:, :, None, :]
+        z = (torch.relu(a) @ weight + bias).reshape(N, L * K, C2)
+        return neighbor_mlp_max(z, own, weight2, bias2)
+
+    if only_new:
+        for _ in range(3):
+            torch.autograd.grad(new(), leaves, up)
+        torch.cuda.synchronize()
+        return []
+    rows_out, flop = [], 2 * N * L * K * (C1 * C2 + C2 * C3)
+    for what in ("fwd", "fwd_bwd"):
+        if what == "fwd":
+            def run(fn):
+                with torch.no_grad():
+                    return fn()
+        else:
+            def run(fn):
+                return torch.autograd.grad(fn(), leaves, up)
+        calls = {"new": lambda: run(new), "old": lambda: run(old), "parent": lambda: run(parent)}
+        row = dict(N=N, L=L, K=K, C1=C1, C2=C2, C3=C3, what=what, rounds=rounds, flop=flop, layers=2,
+                   dtype=str(dtype).replace("torch.", ""))
+        for name in ("old", "parent"):  # a path that cannot hold its edge tensors is recorded, not timed
+            try:
+                got = calls[name]()
+                if what == "fwd":
+                    ref = calls["new"]().float()
+                    assert float((got.float() - ref).abs().max()) <= 2.0 ** -4 * float(ref.abs().max()), name + " differs"
+                    del ref
+                del got
+            except (RuntimeError, torch.OutOfMemoryError) as e:
+                row[f"{name}_error"] = str(e).splitlines()[0]
+                del calls[name]
+            torch.cuda.empty_cache()
+        if what == "fwd":
+            try:
+                A, W1, W2 = torch.randn(N * L * K, C1, generator=gen, device=dev).to(dtype), weight.detach(), weight2.detach()
+                calls["gemm"] = lambda: torch.matmul(torch.matmul(A, W1), W2)
+            except (RuntimeError, torch.OutOfMemoryError) as e:
+                row["gemm_error"] = str(e).splitlines()[0]
+        for name, fn in calls.items():
+            if name != "gemm":
+                row[f"peak_mib_{name}"] = peak_mib(fn)
+        steps = {name: int(min(20, max(1, 50.0 / max(timed(fn, 1), 1e-3)))) for name, fn in calls.items()}  # (warms too)
+        times = {name: [] for name in calls}
+        for _ in range(rounds):
+            for name, fn in calls.items():
+                times[name].append(timed(fn, steps[name]))
+        for name, t in times.items():
+            row[f"ms_{name}"] = round(float(np.median(t)), 4)
+            row[f"ms_min_{name}"] = round(float(np.min(t)), 4)
+            row[f"ms_max_{name}"] = round(float(np.max(t)), 4)
+            if name != "new":
+                row[f"{'new_over' if name == 'gemm' else name + '_over'}_{'gemm' if name == 'gemm' else 'new'}"] = round(
+                    row["ms_new"] / row[f"ms_{name}"] if name == "gemm" else row[f"ms_{name}"] / row["ms_new"], 3)
+        if what == "fwd":
+            row["tflops_new"] = round(flop / (row["ms_new"] * 1e-3) / 1e12, 2)
+        calls.clear()
+        rows_out.append(row)
+        torch.cuda.empty_cache()
+    return rows_out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=1, choices=(1, 2),
+                    help="2: the weight2 form (16-bit dtypes), into profiles/neighbor_mlp2_bench.jsonl")
     ap.add_argument("--out", default=None)
     ap.add_argument("--configs", default=None, help="indices into CONFIGS, comma-separated")
     ap.add_argument("--only-new", action="store_true")
@@ -179,6 +266,20 @@ def main():
     all_configs = CONFIGS if dtype == torch.float32 else CONFIGS + ((256, 256),)  # (the 16-bit kernels go to 256)
     configs = [all_configs[int(i)] for i in args.configs.split(",")] if args.configs else all_configs
     shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
+    if args.layers == 2:
+        if dtype == torch.float32:
+            raise SystemExit("--layers 2 times the 16-bit kernels: give --dtype bfloat16 or float16")
+        configs = [CONFIGS2[int(i)] for i in args.configs.split(",")] if args.configs else CONFIGS2
+        out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                       "neighbor_mlp2_bench.jsonl")
+        with open(os.devnull if args.only_new else out, "w") as f:
+            for N, L in shapes:
+                for cfg in configs:
+                    for row in bench2(N, L, *cfg, args.rounds, dev, args.only_new, dtype):
+                        print(json.dumps(row), flush=True)
+                        f.write(json.dumps(row) + "\n")
+                        f.flush()
+        return
     if args.only_new:  # nothing is measured: no file is opened
         for N, L in shapes:
             for C1, C2 in configs:
